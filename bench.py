@@ -10,6 +10,15 @@ One "step" = zero_grad + forward (0.5x and 1.0x passes, attention fusion,
 RMI + BCE losses as in scripts/train_cityscapes_sota.yml) + backward (+ DDP
 gradient all-reduce and SyncBN when N > 1) + SGD step, on one 1x3x1024x1024
 batch per GPU that is already resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps replays of the step and prints the
+line.  --full adds what else the line can carry, each measured after the timed
+steps: eager steps (eager_ms_per_step), the per-launch roofline, the CPU
+baseline, the bf16-storage step in a child process (value_bf16) and, when
+N > 1, the cost of one SyncBN exchange.  --dump-outputs DIR runs the timed
+step once more after the timed steps, from the state before the first step,
+and writes what it leaves behind (loss, parameters, BatchNorm running
+statistics) as .npy files, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -47,7 +56,7 @@ if _GPUS > 1 and "WORLD_SIZE" not in os.environ and "--cpu-baseline-only" not in
     # `python bench.py --gpus N` (the shape of the driver's N = 1 command) becomes exactly that
     import socket
     with socket.socket() as _sk:
-        _sk.bind(("127.0.0.1", 0))
+        _sk.bind(("", 0))               # free on every address: the rendezvous store listens on all of them
         _port = _sk.getsockname()[1]
     os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(_GPUS),
                               "--master-addr", "127.0.0.1", "--master-port", str(_port), os.path.abspath(__file__)]
@@ -55,7 +64,7 @@ if _GPUS > 1 and "WORLD_SIZE" not in os.environ and "--cpu-baseline-only" not in
 # fp16 storage with dynamic loss scaling is the format of record: it is the reference's own arithmetic (every recipe sets
 # `fp16: true`, scripts/*.yml; train.py:380-381 apex O1), gfx950 runs fp16 MFMA at the bf16 rate, and it sits an order of
 # magnitude closer to the fp32 oracle than bf16 storage.  --dtype bf16 (or SSA_ACT_DTYPE) selects
-# the other build; the default run reports the bf16 step beside the headline (value_bf16).
+# the other build; a --full run reports the bf16 step beside the headline (value_bf16).
 if _DTYPE is not None:
     os.environ["SSA_ACT_DTYPE"] = _DTYPE
 os.environ.setdefault("SSA_ACT_DTYPE", "fp16")
@@ -158,6 +167,56 @@ def secondary_run(args, dtype, timeout_s=420):
         return {"value": None, "error": "secondary %s run exceeded %d s" % (dtype, timeout_s)}
 
 
+# --dump-outputs: parameter-shaped tensors larger than this contribute a fixed sample of this many elements
+DUMP_SAMPLE = 8192
+
+
+def _dump_index(n, seed):
+    """The elements of an n-element tensor that --dump-outputs writes: all of them up to DUMP_SAMPLE, else DUMP_SAMPLE
+    positions drawn by a generator seeded per tensor (the same positions in every run)."""
+    if n <= DUMP_SAMPLE:
+        return torch.arange(n)
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+
+
+def step_state(net, scaler):
+    """Everything the step carries from one replay to the next, on the host: parameters, buffers (BatchNorm running
+    statistics, batch counters) and the dynamic loss scaler's device state.  The momentum buffers are the rest (zero
+    before the first step: restore_step_state zeroes them); the packed filters and the gradient arena are rebuilt
+    inside every step."""
+    ts = list(net.parameters()) + list(net.buffers()) + ([scaler.state] if scaler is not None else [])
+    return [(t, t.detach().to("cpu", copy=True)) for t in ts]
+
+
+def restore_step_state(saved, optim):
+    with torch.no_grad():
+        for t, v in saved:
+            t.copy_(v)
+        for st in optim.state.values():
+            buf = st.get("momentum_buffer")
+            if buf is not None:
+                buf.zero_()
+
+
+def dump_outputs(out_dir, net, loss):
+    """What a caller of the timed step holds after the dumped step, as float32 / float64 .npy files (~11 MB):
+    loss.npy          the step's loss (float64, shape (1,))
+    params.npy        the updated parameters, named_parameters() order, each sampled by _dump_index
+    bn_buffers.npy    every floating-point buffer (BatchNorm running statistics) in full
+    Two runs agree on these to rounding (measured: normwise 2e-7, 8e-6 and 1.4e-6; every element within rtol = atol =
+    1e-3).  The gradients are left out: even from one state, the order of the atomics in the backward pass, amplified
+    through 16-bit storage, leaves them 3 % apart (normwise) between two runs of one build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p.detach().reshape(-1)[_dump_index(p.numel(), i).to(p.device)].float()
+              for i, (_, p) in enumerate(net.named_parameters())]
+    bufs = [b.detach().reshape(-1).float() for _, b in net.named_buffers() if b.is_floating_point()]
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(params).cpu().numpy())
+    np.save(os.path.join(out_dir, "bn_buffers.npy"), torch.cat(bufs).cpu().numpy())
+
+
 def cpu_baseline(timeout_s=240):
     """Run the CPU baseline in a child process under a hard time limit so that a
     misbehaving host (oversubscribed cores) can never stall the benchmark."""
@@ -235,7 +294,13 @@ def main():
                     "trains on 1024x2048: scripts/train_cityscapes_sota.yml:14)")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step in a hipGraph")
-    ap.add_argument("--eager-steps", type=int, default=3, help="eager steps timed after the graph run (0: none)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the eager step, the "
+                    "roofline, the CPU baseline, the bf16 step and (N > 1) the SyncBN exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, run the step once "
+                    "from the initial state and write its loss, sampled parameters and BatchNorm buffers as "
+                    "DIR/<name>.npy")
+    ap.add_argument("--eager-steps", type=int, default=None, help="eager steps timed after the graph run "
+                    "(default: 3 with --full, else 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default=None, help="storage format = library build "
                     "(default fp16 with dynamic loss scaling: the reference's --fp16; SSA_ACT_DTYPE is honoured too)")
@@ -243,6 +308,10 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.eager_steps is None:
+        args.eager_steps = 3 if args.full else 0
     if args.cpu_baseline_only:
         print(json.dumps(_cpu_baseline_impl()))
         return
@@ -265,7 +334,9 @@ def main():
         if world == 1:
             import socket
             with socket.socket() as sk:
-                sk.bind(("127.0.0.1", 0))
+                # free on every address, not only on loopback: the TCPStore of init_process_group listens on all of
+                # them, and a port held on another interface fails it with EADDRINUSE
+                sk.bind(("", 0))
                 os.environ.setdefault("MASTER_PORT", str(sk.getsockname()[1]))
             os.environ.setdefault("RANK", "0")
             os.environ.setdefault("WORLD_SIZE", "1")
@@ -294,6 +365,10 @@ def main():
     # captured step (semseg_amd/amp.py); bf16 storage: scaler is None, scale_loss the identity
     from semseg_amd import amp as samp
     scaler = samp.attach_scaler(optim, torch.device("cuda")) if (samp.fp16_storage() and fused_sgd) else None
+    # --dump-outputs: the state before the first step (seeded initialisation, the same in every run), which the dumped
+    # step starts from -- the timed steps start from a state that earlier steps made, and the order of the fp64 atomics
+    # in those steps differs from run to run, and SGD amplifies it (after 28 steps two runs' parameters were 1 % apart)
+    start_state = step_state(net, scaler) if args.dump_outputs else None
 
     def step():
         optim.zero_grad(set_to_none=True)
@@ -365,7 +440,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_val = float(static_loss.item())
+    loss_scale = scaler.loss_scale() if scaler is not None else None
     ms = dt / args.steps * 1e3
+    if args.dump_outputs:
+        # one more step of the timed path (the replayed graph) from the state before the first step, with the RNG of
+        # its Dropout2d masks reseeded: same arguments, same inputs, the same outputs up to rounding in every run
+        restore_step_state(start_state, optim)
+        torch.manual_seed(0)
+        run()
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, net, float(static_loss.item()))
+    # --full from here on: every leg below runs after the timed steps and the dump
     # the same program without the hipGraph: what a loop that does not go through semseg_amd.graph_training pays
     # (~840 ctypes launches + Python autograd per step, host bound)
     eager_ms = None
@@ -384,7 +470,7 @@ def main():
     # fp64 record (8 replicas x 2 x 720 channels) on the compute stream, all ranks together; x the step's collective
     # count = the time the step spends in exchanges no compute hides (they sit on the critical path of the level chain).
     coll_us = None
-    if dist_on and backend == "nccl" and rccl.ENABLED:
+    if args.full and dist_on and backend == "nccl" and rccl.ENABLED:
         rec = torch.zeros(8 * 2 * 720, dtype=torch.float64, device="cuda")
         c_ = rccl.comm(0)
         for _ in range(20):
@@ -399,7 +485,7 @@ def main():
 
     roof = None
     recs = []
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # Per-launch timing, live: every launch of the group-aware kernels (all conv-class kernels,
         # BatchNorm, sums, resampling) of two eager steps is bracketed by HIP events on its stream
         # inside the library (ssa_profile_begin/_end), keyed by kernel instantiation, with the
@@ -517,12 +603,12 @@ def main():
                     r["flops"] / max(r["total_us"], 1e-3) / 1e6, r["bytes"] / max(r["total_us"], 1e-3) / 1e3), file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
     # the same step on the other storage build (bf16, no loss scaling), timed in a child process at N = 1: one library
     # build per process.  Reported beside the headline, never as `value`.
     other = None
-    if rank == 0 and world == 1 and not args.no_secondary and not dist_on and samp.fp16_storage():
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not dist_on and samp.fp16_storage():
         other = secondary_run(args, "bf16")
 
     if rank == 0:
@@ -543,7 +629,7 @@ def main():
                        "hipgraph": graph is not None, "capture_error": capture_error, "loss": loss_val,
                        "eager_ms_per_step": eager_ms,
                        "optimizer": "ssa_sgd_momentum_step" if fused_sgd else "torch.optim.SGD(foreach)",
-                       "loss_scale": scaler.loss_scale() if scaler is not None else None,
+                       "loss_scale": loss_scale,
                        "library_launches_per_step": launches_per_step,
                        "lib_sha": _lib_sha(),
                        # deferred weight gradients: flushed every N layers onto a side stream (a parallel branch of

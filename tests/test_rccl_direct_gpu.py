@@ -18,7 +18,7 @@ CODE = r"""
 import os, sys, socket, torch, torch.distributed as dist
 sys.path[:0] = [%r, %r]
 with socket.socket() as sk:
-    sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
+    sk.bind(("", 0)); port = sk.getsockname()[1]      # free on every address: the TCPStore listens on all
 os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1")
 torch.cuda.set_device(0)
 dist.init_process_group("gloo")

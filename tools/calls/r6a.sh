@@ -5,15 +5,15 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}" || exit 1
 export TMPDIR=/tmp
 T=${1:-r6a}
-mkdir -p gpurun_out
-timeout 1500 python -m pytest tests -q -m gpu --durations=25 > gpurun_out/${T}_gpu_suite.log 2>&1
+mkdir -p out
+timeout 1500 python -m pytest tests -q -m gpu --durations=25 > out/${T}_gpu_suite.log 2>&1
 echo "suite rc=$?"
-tail -40 gpurun_out/${T}_gpu_suite.log
-timeout 600 python bench.py --steps 20 --warmup 3 > gpurun_out/${T}_bench_line.json 2> gpurun_out/${T}_bench.err
+tail -40 out/${T}_gpu_suite.log
+timeout 600 python bench.py --full --steps 20 --warmup 3 > out/${T}_bench_line.json 2> out/${T}_bench.err
 echo "bench rc=$?"
 python - <<'PY'
 import json
-j = json.load(open("gpurun_out/r6a_bench_line.json")) if True else None
+j = json.load(open("out/r6a_bench_line.json")) if True else None
 r = j.get("roofline") or {}
 print("value", j["value"], "ms", j["ms_per_step"], "dtype", j["dtype"], "bf16", j.get("value_bf16"), j.get("ms_per_step_bf16"), j.get("secondary_error"))
 print("frac", r.get("frac"), "mfma_3x3", json.dumps(r.get("mfma_3x3"))[:900])
@@ -22,4 +22,4 @@ fam = r.get("families", {})
 for k, v in list(fam.items())[:24]:
     print("  %-22s %.3f ms  n=%d  %.0f TF/s %.0f GB/s" % (k, v["ms_per_step"], v["launches_per_step"], v["tflops"], v["hbm_GBps"]))
 PY
-tail -5 gpurun_out/${T}_bench.err
+tail -5 out/${T}_bench.err
