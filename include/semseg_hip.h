@@ -587,7 +587,8 @@ int ssa_bce_fwd(const float* logits, int ld, const int64_t* labels, long P, int 
                 double* acc, float* dlogits, void* stream);
 /* loss = acc[0] / (acc[1] + denom_add) ; writes fp32 scalar                    */
 int ssa_loss_finalize(const double* acc, double denom_add, float* loss, void* stream);
-/* g[i] *= upstream[0] * coef / (acc[1] + denom_add)                            */
+/* g[i] *= upstream[0] * coef / (acc[1] + denom_add); g = 0 when that
+ * denominator is 0 (cross entropy over fully ignored labels: torch's gradient) */
 /* Backward of ssa_bce_fwd WITHOUT its saved gradient: dlogits = (sigmoid - onehot) * mask * upstream * coef /
  * (acc[1] + denom_add), recomputed from the logits (dense [P, C], ld == C, P * C % 4 == 0, 16-byte aligned; otherwise
  * SSA_EUNSUPPORTED and the caller scales the gradient ssa_bce_fwd saved).  loss/rmi.py:103-112's autograd backward. */
@@ -603,7 +604,11 @@ int ssa_scale_grad_to(const float* src, float* dst, long n, const float* upstrea
 /* RMILoss.rmi_lower_bound, loss/rmi.py:139-215 + loss/rmi_utils.py:15-56,
  * 95-107 (K15).  Fused: sigmoid*mask+1e-6 -> 4x4/4 avg pool (pad 2) ->
  * 3x3-neighbourhood Gram matrices in fp64 (never materialising the
- * [B,C,9,65025] stack) -> 9x9 inverse / Cholesky per (b,c) in one wavefront. */
+ * [B,C,9,65025] stack) -> 9x9 inverse / Cholesky per (b,c) in one wavefront.
+ * ssa_rmi_pool: 1 <= C <= 128 classes (the limit of ssa_ce_fwd / ssa_bce_fwd),
+ * ld >= C; above 30 classes the workgroups take the classes in chunks of <= 30
+ * (LDS stays within 64 KB).  Labels outside [0, C) are ignored (label == C
+ * included: Mapillary's ignore label 65).                                    */
 int ssa_rmi_pool(const float* logits, int ld, const int64_t* labels, int B, int H,
                  int W, int C, float* pooled_pr, float* pooled_la, int Hp, int Wp,
                  void* stream);

@@ -198,7 +198,10 @@ __global__ void loss_finalize_kernel(const double* __restrict__ acc, double deno
 // dst = src * upstream * coef / (acc[1] + denom_add)     (src may be dst; otherwise the two do not overlap)
 __global__ void scale_grad_kernel(const float* src, float* dst, long n, const float* __restrict__ upstream,
                                   double coef, const double* __restrict__ acc, double denom_add) {
-  const float s = (float)((double)upstream[0] * coef / (acc[1] + denom_add));
+  // a mean over no pixel (every label ignored, denom_add 0): src is all zero and so is the gradient -- what torch's
+  // nll_loss backward gives for a NaN mean -- not 0 * inf
+  const double den = acc[1] + denom_add;
+  const float s = den != 0.0 ? (float)((double)upstream[0] * coef / den) : 0.f;
   const long n4 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0 ? n >> 2 : 0;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float4 v = reinterpret_cast<const float4*>(src)[i];
@@ -212,16 +215,22 @@ __global__ void scale_grad_kernel(const float* src, float* dst, long n, const fl
 // ------------------------------------------------------------------- RMI
 // pooled_pr[b,c,py,px] = avg over the 4x4 cell (zero padded, /16) of
 //   sigmoid(logit)*mask + 1e-6 ; pooled_la likewise of onehot*mask.
-// One block = one pooled row, 32 pooled columns: stages 4 x 128 input pixels.
+// One block = one pooled row, 32 pooled columns and one chunk of at most kPoolChunk classes: stages 4 x 128 input
+// pixels.  Up to 30 classes the chunk is all of them (one chunk, blockIdx.z = b); from 31 the classes are split into
+// nchunk near-equal chunks of CC classes (blockIdx.z = b * nchunk + chunk), so that the staged probabilities stay
+// within 64 KB of LDS at any class count the losses accept; the labels are staged again by every chunk.
 constexpr int CELLS = 32;
+constexpr int kPoolChunk = 30;      // 4 x 128 x 30 probabilities + 512 labels = 63,488 bytes of LDS
 __global__ __launch_bounds__(NT) void rmi_pool_kernel(const float* __restrict__ logits, int ld,
                                                       const int64_t* __restrict__ labels, int H,
                                                       int W, int C, float* __restrict__ ppr,
-                                                      float* __restrict__ pla, int Hp, int Wp) {
-  SSA_DYN_LDS(float, sm);  // [4][CELLS*4][C] probs, then [4][CELLS*4] labels (as float)
+                                                      float* __restrict__ pla, int Hp, int Wp, int CC, int nchunk) {
+  SSA_DYN_LDS(float, sm);  // [4][CELLS*4][CC] probs, then [4][CELLS*4] labels (as float)
   float* pr = sm;
-  float* lb = sm + 4 * CELLS * 4 * C;
-  const int b = blockIdx.z, py = blockIdx.y, px0 = blockIdx.x * CELLS;
+  float* lb = sm + 4 * CELLS * 4 * CC;
+  const int b = blockIdx.z / nchunk, c0 = (blockIdx.z - b * nchunk) * CC;
+  const int CW = min(CC, C - c0);   // classes of this chunk
+  const int py = blockIdx.y, px0 = blockIdx.x * CELLS;
   const int y0 = py * 4 - 2, x0 = px0 * 4 - 2;
   const int NPX = CELLS * 4;
   // stage labels (as float; -1 = outside / invalid)
@@ -238,29 +247,29 @@ __global__ __launch_bounds__(NT) void rmi_pool_kernel(const float* __restrict__ 
   __syncthreads();
   // four elements per trip, their loads issued before the first exponential (pixels outside the image re-read the
   // image's first logit and store 0): 38 single-load trips per thread at three waves per SIMD ran 65 us for 80 MB
-  const int total = 4 * NPX * C;
+  const int total = 4 * NPX * CW;
   for (int i0 = threadIdx.x; i0 < total; i0 += 4 * NT) {
     float lg[4];
     bool inside[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = i0 + u * NT < total ? i0 + u * NT : i0;
-      const int c = i % C, pxl = i / C;
+      const int c = i % CW, pxl = i / CW;
       const int r = pxl / NPX, xx = pxl - r * NPX;
       const int y = y0 + r, x = x0 + xx;
       inside[u] = y >= 0 && y < H && x >= 0 && x < W;
-      lg[u] = logits[inside[u] ? (((long)b * H + y) * W + x) * ld + c : 0];
+      lg[u] = logits[inside[u] ? (((long)b * H + y) * W + x) * ld + c0 + c : 0];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = i0 + u * NT;
       if (i >= total) break;
-      const float m = lb[i / C] >= 0.f ? 1.f : 0.f;
+      const float m = lb[i / CW] >= 0.f ? 1.f : 0.f;
       pr[i] = inside[u] ? m / (1.f + expf(-lg[u])) + kClipMin : 0.f;
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < CELLS * C; i += NT) {
+  for (int i = threadIdx.x; i < CELLS * CW; i += NT) {
     const int c = i / CELLS, cell = i - c * CELLS;
     const int px = px0 + cell;
     if (px >= Wp) continue;
@@ -270,10 +279,10 @@ __global__ __launch_bounds__(NT) void rmi_pool_kernel(const float* __restrict__ 
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int pxl = r * NPX + cell * 4 + q;
-        sp += pr[pxl * C + c];
-        sl += (lb[pxl] == (float)c) ? 1.f : 0.f;
+        sp += pr[pxl * CW + c];
+        sl += (lb[pxl] == (float)(c0 + c)) ? 1.f : 0.f;
       }
-    const long o = (((long)b * C + c) * Hp + py) * Wp + px;
+    const long o = (((long)b * C + c0 + c) * Hp + py) * Wp + px;
     ppr[o] = sp * (1.f / 16.f);
     pla[o] = sl * (1.f / 16.f);
   }
@@ -583,10 +592,12 @@ __global__ void rmi_bwd_logits_kernel(const float* __restrict__ logits, int ld,
       const int x = (int)(p % W);
       const long t = p / W;
       const int y = (int)(t % H), b = (int)(t / H);
+      // H % 4 == 3 (W % 4 == 3): the last row (column) lies in no pooling window (Hp = H / 4 + 1 cells cover rows
+      // -2 .. 4 Hp - 3 = H - 2) -- its RMI gradient is zero, and py == Hp would read the next plane's first row
       const int py = (y + 2) >> 2, px = (x + 2) >> 2;
       lab[u] = labels[p];
       lg[u] = logits[p * ld + c];
-      dp[u] = dpooled[(((long)b * C + c) * Hp + py) * Wp + px];
+      dp[u] = (py < Hp && px < Wp) ? dpooled[(((long)b * C + c) * Hp + py) * Wp + px] : 0.f;
       old[u] = bce_src ? bce_src[i] * kb : (accumulate ? dlogits[i] : 0.f);
     }
 #pragma unroll
@@ -699,10 +710,12 @@ int ssa_rmi_pool(const float* logits, int ld, const int64_t* labels, int B, int 
                  float* pooled_pr, float* pooled_la, int Hp, int Wp, void* stream) {
   if (!logits || !labels || !pooled_pr || !pooled_la) return SSA_EINVAL;
   if (Hp != H / 4 + 1 || Wp != W / 4 + 1) return SSA_EINVAL;
-  const size_t lds = (size_t)(4 * CELLS * 4 * C + 4 * CELLS * 4) * sizeof(float);
-  if (lds > 64000) return SSA_EUNSUPPORTED;
-  hipLaunchKernelGGL(rmi_pool_kernel, dim3((Wp + CELLS - 1) / CELLS, Hp, B), dim3(NT), lds,
-                     (hipStream_t)stream, logits, ld, labels, H, W, C, pooled_pr, pooled_la, Hp, Wp);
+  if (B <= 0 || C <= 0 || C > 128 || ld < C) return SSA_EINVAL;
+  // C <= 30: one chunk of all C classes (the launch of the Cityscapes path); beyond, near-equal chunks of <= 30
+  const int nchunk = (C + kPoolChunk - 1) / kPoolChunk, CC = (C + nchunk - 1) / nchunk;
+  const size_t lds = (size_t)(4 * CELLS * 4 * CC + 4 * CELLS * 4) * sizeof(float);
+  hipLaunchKernelGGL(rmi_pool_kernel, dim3((Wp + CELLS - 1) / CELLS, Hp, B * nchunk), dim3(NT), lds,
+                     (hipStream_t)stream, logits, ld, labels, H, W, C, pooled_pr, pooled_la, Hp, Wp, CC, nchunk);
   SSA_LAUNCH_CHECK();
   return SSA_OK;
 }

@@ -67,6 +67,29 @@ def test_confusion_matrix_on_device():
     assert np.array_equal(fast_hist_dev(pred, gts.cuda(), C).cpu().numpy(), want)
 
 
+@pytest.mark.parametrize("ign", [65, 255])
+def test_confusion_matrix_65_classes(ign):
+    """The Mapillary evaluation tail: 65 classes (a 65 x 65 LDS histogram), ignore label 65 (= C, out of range) or
+    255, bit-exact against the oracle's fast_hist on a ragged pixel count, with exact ties between classes."""
+    from oracle.data import fast_hist, eval_predictions
+    from semseg_amd.utils import confusion_matrix
+    g = torch.Generator().manual_seed(ign)
+    B, C, H, W = 2, 65, 37, 61
+    logits = torch.randn(B, C, H, W, generator=g) * 3
+    logits[:, 64] = logits[:, 40]                     # exact ties: the first maximum must win
+    gts = torch.randint(0, C, (B, H, W), generator=g)
+    gts[torch.rand(B, H, W, generator=g) < 0.15] = ign
+    gts[1, 3:9] = ign
+    pred_ref = eval_predictions(logits)
+    assert torch.equal(pred_ref, logits.max(1)[1])
+    want = fast_hist(pred_ref.numpy().flatten(), gts.numpy().flatten(), C)
+    assert want.sum() == int((gts != ign).sum())
+    nhwc_view = logits.permute(0, 2, 3, 1).contiguous().cuda().permute(0, 3, 1, 2)
+    hist, pred = confusion_matrix(nhwc_view, gts.cuda(), C, return_predictions=True)
+    assert torch.equal(pred.cpu().long(), pred_ref)
+    assert np.array_equal(hist.cpu().numpy(), want)
+
+
 def test_pipeline_tail_on_device_is_bit_exact():
     """ssa_image_u8_crop_flip_normalize / ssa_label_u8_crop_flip against the oracle (pinned to PIL +
     torch in tests/test_data_cpu.py) on the golden image and on a full-size 1024x2048 frame: the

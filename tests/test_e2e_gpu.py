@@ -36,13 +36,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _synth(B, H, W, seed):
+def _synth(B, H, W, seed, C=19, ign=255):
     g = torch.Generator().manual_seed(seed)
     images = torch.randn(B, 3, H, W, generator=g)
     bs = 32
-    blocks = torch.randint(0, 19, (B, (H + bs - 1) // bs, (W + bs - 1) // bs), generator=g)
+    blocks = torch.randint(0, C, (B, (H + bs - 1) // bs, (W + bs - 1) // bs), generator=g)
     gts = blocks.repeat_interleave(bs, 1).repeat_interleave(bs, 2)[:, :H, :W].clone()
-    gts[torch.rand(B, H, W, generator=g) < 0.1] = 255
+    gts[torch.rand(B, H, W, generator=g) < 0.1] = ign
     return images, gts.long()
 
 
@@ -63,18 +63,20 @@ def _rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def _run(backend, sd, images, gts, train, device="cpu"):
+def _run(backend, sd, images, gts, train, device="cpu", C=19, ign=255):
     from semseg_amd import ops
     from semseg_amd.config import cfg
     from semseg_amd.loss import RMILoss
     from semseg_amd.network import ocrnet
     prev = ops._BACKEND
     ops._set_backend_for_tests(backend)
+    saved_nc = cfg.DATASET.NUM_CLASSES
     try:
         cfg.LOSS.SUPERVISED_MSCALE_WT = 0.05
         cfg.MODEL.N_SCALES = None
         cfg.MODEL.BNFUNC = None
-        net = ocrnet.HRNet_Mscale(19, RMILoss(num_classes=19, ignore_index=255))
+        cfg.DATASET.NUM_CLASSES = C             # the OCR head's width (network/ocrnet.py reads it from the config)
+        net = ocrnet.HRNet_Mscale(C, RMILoss(num_classes=C, ignore_index=ign))
         net.load_state_dict(sd)
         for m in net.modules():
             if isinstance(m, torch.nn.Dropout2d):
@@ -102,6 +104,7 @@ def _run(backend, sd, images, gts, train, device="cpu"):
         stats = {k: v.detach().float().cpu() for k, v in net.state_dict().items() if "running_" in k}
         return float(loss.detach()), grads, stats
     finally:
+        cfg.DATASET.NUM_CLASSES = saved_nc
         ops._set_backend_for_tests(prev)
 
 
@@ -163,13 +166,50 @@ def test_eval_op_by_op(setup):
 
 
 def test_train_step(setup):
+    _check_train_step(*setup)
+
+
+@pytest.fixture(scope="module")
+def setup65():
+    """Mapillary's head: 65 classes, ignore label 65 (= C), B = 2 at test_train_step's 256 x 256 (at 128 x 128 the
+    random network's gradient cosines are noisier than the margins of test_train_step's bounds, on both paths)."""
+    from semseg_amd.config import cfg
+    from semseg_amd.loss import RMILoss
+    from semseg_amd.network import ocrnet
+    from oracle.model import Net
+    cfg.LOSS.SUPERVISED_MSCALE_WT = 0.05
+    cfg.MODEL.N_SCALES = None
+    cfg.MODEL.BNFUNC = None
+    saved_nc = cfg.DATASET.NUM_CLASSES
+    cfg.DATASET.NUM_CLASSES = 65
+    try:
+        net = ocrnet.HRNet_Mscale(65, RMILoss(num_classes=65, ignore_index=65))
+    finally:
+        cfg.DATASET.NUM_CLASSES = saved_nc
+    shapes = [(k, tuple(v.shape)) for k, v in net.state_dict().items()]
+    sd = parity_state_dict(shapes, seed=0)
+    images, gts = _synth(2, 256, 256, seed=65, C=65, ign=65)
+    with torch.no_grad():
+        Net(sd, 65, training=True, bn_momentum=1.0, criterion="ce", ignore_index=65).two_scale_forward(images, gts)
+    return sd, images, gts
+
+
+def test_training_65_classes(setup65):
+    """One HRNet_Mscale(65, RMILoss(num_classes=65, ignore_index=65)) training step against the oracle with
+    test_train_step's assertions: the RMI pool in three class chunks and the 65-wide classifier convs' data and weight
+    gradients (output channels padded to 72)."""
+    sd, images, gts = setup65
+    assert int((gts == 65).sum()) > 0
+    _check_train_step(sd, images, gts, C=65, ign=65)
+
+
+def _check_train_step(sd, images, gts, C=19, ign=255):
     from semseg_amd import ops
     from oracle_backend import OracleBackend
     from bf16_emu_backend import Bf16EmuBackend
-    sd, images, gts = setup
-    lr, gr, sr = _run(OracleBackend(), sd, images, gts, True)
-    le, ge, se = _run(Bf16EmuBackend(), sd, images, gts, True)
-    lh, gh, sh = _run(ops.HipBackend(), sd, images, gts, True, device="cuda")
+    lr, gr, sr = _run(OracleBackend(), sd, images, gts, True, C=C, ign=ign)
+    le, ge, se = _run(Bf16EmuBackend(), sd, images, gts, True, C=C, ign=ign)
+    lh, gh, sh = _run(ops.HipBackend(), sd, images, gts, True, device="cuda", C=C, ign=ign)
     print("train loss hip %.6f emu %.6f oracle %.6f" % (lh, le, lr))
     assert abs(lh - lr) <= 2e-3 * abs(lr) + 2 * abs(le - lr)
 

@@ -864,10 +864,10 @@ def test_sum_act():
 
 
 # -------------------------------------------------------------------- OCR
-def test_ocr_gather():
+def _ocr_gather_case(K, H, W):
     from oracle import ops as O
     hb = _hb()
-    B, C, K, H, W = 2, 512, 19, 24, 28
+    B, C = 2, 512
     feats = _rand(B, C, H, W, seed=1)
     logits = torch.randn(B, K, H, W) * 2.0
     fr = feats.clone().requires_grad_(True)
@@ -883,6 +883,16 @@ def test_ocr_gather():
     check_close("gather_fwd", out.permute(0, 2, 1), ctx[..., 0], 1e-2, 4e-3)
     check_close("gather_dfeats", nchw(fd.grad.float()), fr.grad, 2e-2, 6e-3)
     check_close("gather_dlogits", nchw(ld.grad), lr.grad, 2e-2, 8e-3)
+
+
+def test_ocr_gather():
+    _ocr_gather_case(19, 24, 28)
+
+
+def test_ocr_gather_65_classes():
+    """Mapillary's 65 regions (padded to 96 in the probability operand) over a ragged 13 x 21 = 273 pixels: softmax
+    over HW per class, the context product and both gradients (ssa_softmax_hw_* and the row dots)."""
+    _ocr_gather_case(65, 13, 21)
 
 
 @pytest.mark.parametrize("K,H,W,fused", [(19, 20, 24, True), (65, 9, 31, True), (19, 3, 5, True), (96, 8, 16, True),
@@ -988,3 +998,198 @@ def test_bce_rmi(do_rmi, shape):
     torch.cuda.synchronize()
     check_close("bce_rmi(%s)" % do_rmi, out.view(1), loss.view(1), 1e-4, 1e-4)
     check_close("bce_rmi_grad(%s)" % do_rmi, nchw(ld.grad), lr.grad, 2e-3, 1e-3)
+
+
+# Class counts beyond Cityscapes' 19 (Mapillary: 65 classes, ignore label 65 = C, out of range like 255), label edges,
+# saturated logits and the fp16 step's loss-scaled upstream gradient (65536 at the start of apex-style dynamic scaling).
+def _label_map(kind, B, H, W, C, ign, seed=0):
+    """`blocks8`: random 8 x 8 blocks with 10 % scattered ignore; `blocks`: large blocks (a quarter of the crop's
+    height) with an ignored band, as real scenes have; `single`: one class everywhere but a few ignored pixels;
+    `ignored`: every pixel ignored."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == "blocks8":
+        lab = _labels(B, H, W, C, seed=seed)
+        lab[lab == 255] = ign
+        return lab
+    if kind == "blocks":
+        bs = max(4, H // 4)
+        blocks = torch.randint(0, C, (B, (H + bs - 1) // bs, (W + bs - 1) // bs), generator=g)
+        lab = blocks.repeat_interleave(bs, 1).repeat_interleave(bs, 2)[:, :H, :W].clone()
+        lab[:, :, W // 3:W // 3 + 3] = ign
+        return lab.long()
+    if kind == "single":
+        lab = torch.full((B, H, W), int(torch.randint(0, C, (1,), generator=g)), dtype=torch.long)
+        lab[:, 0, :3] = ign
+        return lab
+    assert kind == "ignored"
+    return torch.full((B, H, W), ign, dtype=torch.long)
+
+
+def _logits_on_device(logits, sliced):
+    """NHWC fp32 on the device: dense, or (sliced) channels 2..C+1 of a wider NHWC buffer (ld = C + 5)."""
+    x = nhwc(logits)
+    if not sliced:
+        return x.to(DEV).requires_grad_(True)
+    B, H, W, C = x.shape
+    wide = torch.randn(B, H, W, C + 5)
+    wide[..., 2:2 + C] = x
+    return wide.to(DEV).requires_grad_(True)
+
+
+def _grad_of(ld, C, sliced):
+    g = ld.grad[..., 2:2 + C] if sliced else ld.grad
+    if sliced:      # nothing outside the slice is touched
+        assert float(ld.grad[..., :2].abs().max()) == 0.0 and float(ld.grad[..., 2 + C:].abs().max()) == 0.0
+    return nchw(g.contiguous())
+
+
+def _fwd_input(ld, C, sliced):
+    return ld[..., 2:2 + C] if sliced else ld
+
+
+@pytest.mark.parametrize("scale,up", [(3.0, 1.7), (60.0, 65536.0), (3.0, 65536.0), (60.0, 1.7)])
+@pytest.mark.parametrize("sliced", [False, True])
+@pytest.mark.parametrize("ign", ["255", "C"])
+@pytest.mark.parametrize("C", [19, 65, 128])
+def test_cross_entropy_classes(C, ign, sliced, scale, up):
+    """ssa_ce_fwd at 19 / 65 / 128 classes (from 65 the [256][C] tile needs the raised LDS limit), ignore label 255 or
+    C, B = 2 with 2 x 17 x 23 = 782 pixels (not a multiple of the 256-pixel tile), logits dense or a channel slice of a
+    wider NHWC buffer, moderate and saturated logits (logsumexp at |x| ~ 60 x 4), upstream 1.7 or the loss scale."""
+    from oracle import ops as O
+    hb = _hb()
+    B, H, W = 2, 17, 23
+    ign = 255 if ign == "255" else C
+    g = torch.Generator().manual_seed(C + int(scale))
+    logits = torch.randn(B, C, H, W, generator=g) * scale
+    lab = _label_map("blocks8", B, H, W, C, ign, seed=C)
+    lr = logits.clone().requires_grad_(True)
+    loss = O.cross_entropy(lr, lab, ign)
+    (loss * up).backward()
+    assert torch.isfinite(loss) and torch.isfinite(lr.grad).all()
+    ld = _logits_on_device(logits, sliced)
+    out = hb.CrossEntropyFn.apply(_fwd_input(ld, C, sliced), lab.to(DEV), ign)
+    (out * up).backward()
+    torch.cuda.synchronize()
+    check_close("ce", out.view(1), loss.view(1), 1e-5, 1e-5)
+    check_close("ce_grad", _grad_of(ld, C, sliced), lr.grad, 1e-4, 1e-4)
+
+
+@pytest.mark.parametrize("C", [19, 65])
+def test_cross_entropy_fully_ignored(C):
+    """Every label ignored: the reference's nll_loss mean over zero pixels is NaN and its gradient is zero; the
+    kernels give the same (not 0 * inf in the gradient)."""
+    from oracle import ops as O
+    hb = _hb()
+    B, H, W = 2, 9, 13
+    logits = torch.randn(B, C, H, W) * 3
+    lab = _label_map("ignored", B, H, W, C, C)
+    lr = logits.clone().requires_grad_(True)
+    loss = O.cross_entropy(lr, lab, C)
+    (loss * 1.7).backward()
+    ld = nhwc(logits).to(DEV).requires_grad_(True)
+    out = hb.CrossEntropyFn.apply(ld, lab.to(DEV), C)
+    (out * 1.7).backward()
+    torch.cuda.synchronize()
+    assert torch.isnan(loss) and torch.isnan(out.cpu())
+    assert torch.equal(nchw(ld.grad).cpu(), lr.grad), float((nchw(ld.grad).cpu() - lr.grad).abs().max())
+
+
+def _bce_rmi_case(B, C, H, W, route, ign, kind, scale, up, do_rmi, seed=0):
+    """BceRmiFn against oracle.ops.rmi_loss.  route "dense": the forward saves no gradient, the backward recomputes it;
+    "slice" (ld != C) and "odd" (P * C % 4 != 0): the forward saves the un-normalised gradient.  The route is asserted."""
+    from oracle import ops as O
+    hb = _hb()
+    sliced = route == "slice"
+    if route == "odd":
+        assert (B * H * W * C) % 4, (B, H, W, C)
+    g = torch.Generator().manual_seed(1000 * seed + C)
+    logits = torch.randn(B, C, H, W, generator=g) * scale
+    lab = _label_map(kind, B, H, W, C, ign, seed=seed + 3)
+    lr = logits.clone().requires_grad_(True)
+    loss = O.rmi_loss(lr, lab, C, do_rmi=do_rmi)
+    (loss * up).backward()
+    # the cases stay where the reference's Cholesky is defined
+    assert torch.isfinite(loss) and torch.isfinite(lr.grad).all(), "oracle not finite"
+    ld = _logits_on_device(logits, sliced)
+    out = hb.BceRmiFn.apply(_fwd_input(ld, C, sliced), lab.to(DEV), do_rmi, 0.5)
+    assert out.grad_fn.recompute == (route == "dense"), (route, out.grad_fn.recompute)
+    (out * up).backward()
+    torch.cuda.synchronize()
+    check_close("bce_rmi(%s)" % do_rmi, out.view(1), loss.view(1), 1e-4, 1e-4)
+    check_close("bce_rmi_grad(%s)" % do_rmi, _grad_of(ld, C, sliced), lr.grad, 2e-3, 1e-3)
+
+
+# (C, route): every class count with the dense route and a saved-gradient route; P * C is odd-free at 128 classes
+_BCE_ROUTES = [(C, r) for C in (19, 30, 31, 65, 128) for r in ("dense", "slice", "odd") if not (C == 128 and r == "odd")]
+
+
+@pytest.mark.parametrize("do_rmi", [False, True])
+@pytest.mark.parametrize("ign", ["255", "C"])
+@pytest.mark.parametrize("C,route", _BCE_ROUTES)
+def test_bce_rmi_classes(C, route, ign, do_rmi):
+    """19 / 30 classes: one chunk of the RMI pool; 31 / 65 / 128: two, three and five chunks."""
+    H, W = (19, 27) if route == "odd" else (20, 28)
+    _bce_rmi_case(1, C, H, W, route, 255 if ign == "255" else C, "blocks8", 2.0, 0.4, do_rmi)
+
+
+# H and W through every remainder mod 4 (the pool pads by 2), the smallest pooled grid (H = 8: Hp = 3), B = 2
+@pytest.mark.parametrize("do_rmi", [False, True])
+@pytest.mark.parametrize("C", [19, 65])
+@pytest.mark.parametrize("B,H,W", [(2, 8, 13), (1, 9, 22), (2, 10, 35), (1, 11, 40), (2, 15, 9), (1, 12, 11)])
+def test_bce_rmi_geometry(B, H, W, C, do_rmi):
+    route = "dense" if (B * H * W * C) % 4 == 0 else "odd"
+    _bce_rmi_case(B, C, H, W, route, C, "blocks8", 2.0, 0.4, do_rmi, seed=H)
+
+
+@pytest.mark.parametrize("scale,up", [(2.0, 0.4), (30.0, 65536.0), (30.0, 0.4), (2.0, 65536.0)])
+@pytest.mark.parametrize("kind", ["blocks8", "blocks", "single", "ignored"])
+@pytest.mark.parametrize("C", [19, 65])
+def test_bce_rmi_label_maps(C, kind, scale, up):
+    """Realistic and degenerate label maps, saturated logits (|x| ~ 30: probabilities at the 1e-6 clip or 1.0, the
+    9 x 9 inverse and Cholesky near the 5e-4 I regulariser) and the loss-scaled upstream; B = 2, ignore label C."""
+    _bce_rmi_case(2, C, 24, 36, "dense", C, kind, scale, up, True, seed=7)
+
+
+@pytest.mark.parametrize("do_rmi", [False, True])
+def test_bce_rmi_wide_crop(do_rmi):
+    """A pooled width of 651 (> ~620): ssa_rmi_gram's raised-LDS branch; the odd pixel count takes the saved route."""
+    _bce_rmi_case(1, 19, 9, 2601, "odd", 255, "blocks", 2.0, 0.4, do_rmi)
+
+
+# The full 1024 x 1024 crop (grid-stride loops, 512 workgroups' same-address fp64 atomics of the dense BCE kernel) against
+# the CPU oracle.  Not named like the small loss tests: the emulated selection (test_emu_selected_cpu.py) leaves them out.
+@pytest.mark.skipif(bool(os.environ.get("SSA_EMU")), reason="full crop: GPU only")
+@pytest.mark.parametrize("B,C,ign", [(1, 19, 255), (2, 65, 65)])
+def test_full_crop_losses(B, C, ign):
+    from oracle import ops as O
+    hb = _hb()
+    H = W = 1024
+    g = torch.Generator().manual_seed(C)
+    logits = torch.randn(B, C, H, W, generator=g) * 2
+    lab = _label_map("blocks", B, H, W, C, ign, seed=C)
+    lab[torch.rand(B, H, W, generator=g) < 0.05] = ign
+    ld = nhwc(logits).to(DEV)
+    labd = lab.to(DEV)
+    # masked BCE + RMI (dense: the recomputing route), upstream = the loss scale
+    lr = logits.clone().requires_grad_(True)
+    loss = O.rmi_loss(lr, lab, C, do_rmi=True)
+    (loss * 65536.0).backward()
+    assert torch.isfinite(loss) and torch.isfinite(lr.grad).all()
+    x = ld.clone().requires_grad_(True)
+    out = hb.BceRmiFn.apply(x, labd, True, 0.5)
+    assert out.grad_fn.recompute
+    (out * 65536.0).backward()
+    torch.cuda.synchronize()
+    check_close("full_bce_rmi", out.view(1), loss.view(1), 1e-4, 1e-4)
+    check_close("full_bce_rmi_grad", nchw(x.grad).cpu(), lr.grad, 2e-3, 1e-3)
+    del lr, x, out
+    # cross entropy
+    lr = logits.clone().requires_grad_(True)
+    loss = O.cross_entropy(lr, lab, ign)
+    (loss * 65536.0).backward()
+    x = ld.clone().requires_grad_(True)
+    out = hb.CrossEntropyFn.apply(x, labd, ign)
+    (out * 65536.0).backward()
+    torch.cuda.synchronize()
+    check_close("full_ce", out.view(1), loss.view(1), 1e-5, 1e-5)
+    check_close("full_ce_grad", nchw(x.grad).cpu(), lr.grad, 1e-4, 1e-4)

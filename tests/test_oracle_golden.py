@@ -53,6 +53,37 @@ def test_cross_entropy_matches_reference():
     check_close("ce grad", lg.grad, g["grad"], 1e-6, 1e-6)
 
 
+def _loss65_inputs():
+    """tests/golden/make_golden_loss65.py's inputs(): the logits are regenerated from the seed, not stored."""
+    g = torch.Generator().manual_seed(65)
+    logits = torch.randn(2, 65, 15, 18, generator=g) * 2
+    return logits
+
+
+@pytest.mark.parametrize("which", ["bce", "bce_rmi", "ce"])
+def test_losses_at_65_classes_match_reference(which):
+    """Mapillary's class count and ignore label (65 = C): RMILoss(num_classes=65, ignore_index=65) with do_rmi False /
+    True and CrossEntropyLoss2d(ignore_index=65) of the reference, at H % 4 == 3 -- the oracle the GPU loss tests
+    compare against is the reference there too."""
+    from oracle import ops as O
+    g = _load("loss65_golden.pt")
+    logits = _loss65_inputs()
+    assert float(logits.double().sum()) == pytest.approx(float(g["logits_sum"]), abs=1e-9)
+    assert float(logits.double().abs().sum()) == pytest.approx(float(g["logits_abs_sum"]), abs=1e-9)
+    gts = g["gts"].long()
+    assert int((gts == 65).sum()) > 0 and int(gts.max()) == 65
+    lg = logits.clone().requires_grad_(True)
+    if which == "ce":
+        loss = O.cross_entropy(lg, gts, 65)
+        key = "ce"
+    else:
+        loss = O.rmi_loss(lg, gts, 65, do_rmi=which == "bce_rmi")
+        key = "rmi%d" % (which == "bce_rmi")
+    loss.backward()
+    check_close("loss65 " + which, loss.view(1), g["loss_" + key].view(1), 1e-6, 1e-6)
+    check_close("loss65 grad " + which, lg.grad, g["grad_" + key], 1e-6, 1e-6)
+
+
 @pytest.fixture(scope="module")
 def gold():
     return _load("mscale_golden.pt")

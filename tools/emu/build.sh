@@ -22,5 +22,17 @@ for f in "$SRC"/*.hip "$HERE/emu_runtime.cpp"; do
   fi
 done
 for p in $pids; do wait "$p"; done
-$CXX -shared -fPIC -o "$OUT/libsemseg_emu.so" $objs -lpthread
-echo "built $OUT/libsemseg_emu.so"
+# Several processes may run this at once (every rank of a multi-process test calls it) while others already have the
+# library loaded or are about to load it.  So: relink only when an object is newer than the library, and link to a
+# temporary name that is renamed into place -- the linker removes its output file before writing it, and a process
+# that opened the library in that window found no file.
+LIB="$OUT/libsemseg_emu.so"
+relink=0
+[ -f "$LIB" ] || relink=1
+for o in $objs; do if [ "$o" -nt "$LIB" ]; then relink=1; fi; done
+if [ "$relink" = 1 ]; then
+  tmp="$LIB.tmp.$$"
+  $CXX -shared -fPIC -o "$tmp" $objs -lpthread || { rm -f "$tmp"; exit 1; }
+  mv -f "$tmp" "$LIB"
+fi
+echo "built $LIB"
