@@ -152,11 +152,12 @@ int ssa_conv_tile_strip(int units);
 int ssa_conv2d_tile_p(const ssa_conv_desc* d, const void* x, const void* w_frag, const float* bias, void* y,
                       double* stats, const void* aux, int ldaux, const float* coef, int aux_mode, void* stream);
 
-/* Halo-chunk implicit GEMM for the large-channel 3x3 / 1x1 stride-1 "same" convs
- * of the OCR and attention heads (Cin >= 192, Cin % 48 == 0 or % 64 == 0):
- * 256-pixel x 128-channel workgroup tiles, the input halo tile of each 48/64
- * channel chunk staged in LDS once for all 9 taps, the filter (fragment order,
- * ssa_pack_filter mode 2/3) streamed by global_load_lds.  bf16 or fp32 output;
+/* Large-channel 3x3 / 1x1 stride-1 "same" convs of the OCR and attention heads
+ * (Cin >= 192, Cin % 48 == 0 or % 64 == 0).  1x1: halo-chunk implicit GEMM,
+ * 256-pixel x 128-channel workgroup tiles, the input tile of each 48/64 channel
+ * chunk staged in LDS, the filter (fragment order, ssa_pack_filter mode 2/3)
+ * streamed by global_load_lds; bf16 or fp32 output.  3x3: forwarded to
+ * ssa_conv2d_halo_reg, so only the problems it supports are supported here.
  * stats as for ssa_conv2d_tile (bf16 output only).                             */
 int ssa_conv2d_halo_supported(const ssa_conv_desc* d);
 int ssa_conv2d_halo(const ssa_conv_desc* d, const void* x, const void* w_frag,
@@ -174,14 +175,13 @@ int ssa_conv2d_gemm_wide_supported(const ssa_conv_desc* d);
 int ssa_conv2d_gemm_wide(const ssa_conv_desc* d, const void* x, const void* w_frag, const float* bias,
                          void* y, double* stats, void* stream);
 
-/* Second geometry for the 3x3 stride-1 "same" convs of the OCR / attention heads and their data gradients
+/* Register-fed kernel for the 3x3 stride-1 "same" convs of the OCR / attention heads and their data gradients
  * (conv3x3_ocr 720->512, attn 512->256 / 256->256; network/ocrnet.py:54-58, network/utils.py:348-357): 128 pixels x
  * 256 channels per 4-wave workgroup, 128 x 64 per wave (4 x 2 MFMA 32x32x16 tiles); the filter fragments go straight
  * from global memory into the MFMA operand registers through a ring six k-steps deep (they never touch LDS), the input
  * halo tile by LDS DMA, double buffered per 48 / 64-channel chunk: one workgroup barrier per chunk
  * (csrc/conv_halo_reg.hip).  Same operands as ssa_conv2d_halo; 16-bit output only; stats as for ssa_conv2d_tile.
- * ssa_conv2d_halo forwards the 3x3 problems this entry point supports (SSA_HALO3_REG=0 keeps them on the 256 x 128
- * LDS-ring kernel).                                                                                              */
+ * ssa_conv2d_halo forwards every 3x3 problem here.                                                                */
 int ssa_conv2d_halo_reg_supported(const ssa_conv_desc* d);
 int ssa_conv2d_halo_reg(const ssa_conv_desc* d, const void* x, const void* w_frag, const float* bias,
                         void* y, double* stats, void* stream);
@@ -397,25 +397,6 @@ int ssa_bn_bwd_apply(const void* x, int ldx, const void* dz, int lddz,
                      long pix_per_img, float* dgamma, float* dbeta,
                      float param_grad_scale, const float* mask_scale,
                      const float* mask_shift, int accumulate_param_grads, const void* sign_mask, void* stream);
-/* Backward reduce + apply as ONE launch for the BatchNorm layers whose sums no conv epilogue has formed (bn2 of a
- * BasicBlock, network/hrnetv2.py:53-64): phase 1 forms sum g / sum g xhat as ssa_bn_bwd_reduce does, a grid-wide
- * rendezvous (one atomic ticket per workgroup) follows, phase 2 applies them to the chunk the workgroup still holds in
- * registers -- (x, dz, mask) are read once instead of twice.  Same arguments as ssa_bn_bwd_apply (sums: zeroed
- * [nrep][2][C], accumulated here) plus `ticket`, one zeroed 32-bit word per call.  Every workgroup of the launch must be
- * able to be resident at once: ssa_bn_bwd_fused_blocks(P, C) = workgroups the problem takes (0: unsupported -- more
- * than one chunk per workgroup, emulation build), ssa_bn_bwd_fused_capacity() = workgroups the device holds; the caller
- * keeps a bracket's total within it and takes the two-launch form otherwise, and whenever a SyncBN exchange has to happen
- * between the halves.  A workgroup that waits ~1 s gives up and counts itself: ssa_bn_bwd_fused_timeouts (0 = never). */
-int ssa_bn_bwd_fused_blocks(long P, int C);
-int ssa_bn_bwd_fused_capacity(void);
-int ssa_bn_bwd_fused_timeouts(unsigned* out);
-int ssa_bn_bwd_fused(const void* x, int ldx, const void* dz, int lddz, const void* z, int ldz,
-                     void* dx, int lddx, void* dres, int lddres, long P, int C, const float* gamma,
-                     const float* mean, const float* invstd, double* sums, int nrep,
-                     double count, int relu, const float* post, long pix_per_img, float* dgamma,
-                     float* dbeta, float param_grad_scale, const float* mask_scale,
-                     const float* mask_shift, int accumulate_param_grads, const void* sign_mask, void* ticket,
-                     void* stream);
 /* dgamma[c] = sums[C+c], dbeta[c] = sums[c] (fp64 -> fp32)                     */
 int ssa_bn_param_grads(const double* sums, int C, float* dgamma, float* dbeta,
                        void* stream);

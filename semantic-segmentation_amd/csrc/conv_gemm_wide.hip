@@ -16,7 +16,7 @@
 //     the whole L1), 32 MFMAs per wave between barriers, the next stage's DMAs issued at the top of the stage, the
 //     stage ends in  s_waitcnt vmcnt(0) ; s_barrier.  <CK = 32, RING = 4> keeps three stages in flight and ends a stage
 //     in  s_waitcnt vmcnt(K) ; s_barrier  with K = the DMAs issued after the stage after next (memory operations retire
-//     in order) -- conv_halo_gemm.hip's 3x3 protocol with one "tap" -- and reads its first fragments across the barrier;
+//     in order) and reads its first fragments across the barrier;
 //   * the pixel tile lies in LDS pixel-major, 2 CK bytes per pixel and stage, the 16-byte piece q of pixel p in slot
 //     q ^ ((p >> 1) & 7) (CK = 64) / q ^ ((p >> 2) & 3) (CK = 32): the 16 lanes a ds_read_b128 services together read
 //     one q of 16 pixels with distinct p mod 16, i.e. 16 distinct 16-byte slots of the 256-byte bank row (a DMA fills
@@ -27,7 +27,6 @@
 #include "common.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
-#include <stdlib.h>
 
 #ifndef SSA_WIDE_CK          // experiment builds (tools/expbuild.sh) compile the other stage form: -DSSA_WIDE_CK=32 -DSSA_WIDE_RING=4
 #define SSA_WIDE_CK 64
@@ -273,23 +272,13 @@ bool wide_shape_ok(const ssa_conv_desc* d) {
 
 extern "C" {
 
-// 1 = the wide kernel takes this problem AND is the better choice for it:
-//   * the large head convs with at least two 256-channel tiles of output (with one, a 256^2 + 128^2 training level is
-//     320 workgroups = 1.25 rounds on 256 CUs; conv_halo_gemm.hip's 256 x 128 tile gives 640);
-//   * (switchable, off: SSA_GEMM_WIDE_SMALL) the small-channel 1x1 convs of layer1 / the fuse layers.
+// 1 = the wide kernel takes this problem AND is the better choice for it: the large head convs with at least two
+// 256-channel tiles of output (with one, a 256^2 + 128^2 training level is 320 workgroups = 1.25 rounds on 256 CUs;
+// conv_halo_gemm.hip's 256 x 128 tile gives 640).
 int ssa_conv2d_gemm_wide_supported(const ssa_conv_desc* d) {
   if (!wide_shape_ok(d)) return 0;
   if ((long)d->B * d->H * d->W < 16384) return 0;
-  // SSA_GEMM_WIDE_SMALL: 0 (default) = the large head convs only; 1 = + the 1x1 convs no halo kernel takes; 2 = + the
-  // narrow-output 1x1 convs of layer1 (256 -> 64) that the 256 x 128 kernel takes.  Measured (round 6, call H): the 20 /
-  // 28 launches that move are 10-20 us each on either kernel -- 20.21 / 20.23 ms per step against 20.21 / 20.23 -- so
-  // they stay where the emulated test-suite already exercises them.
-  static const int small = getenv("SSA_GEMM_WIDE_SMALL") ? atoi(getenv("SSA_GEMM_WIDE_SMALL")) : 0;
-  if (d->Cout > 256) return 1;
-  if (small <= 0 || d->Cout < 64) return 0;
-  const bool halo_takes = d->Cin >= 192 && (d->Cin % 48 == 0 || d->Cin % 64 == 0) && d->W >= 32;
-  if (!halo_takes) return 1;
-  return small >= 2 && d->Cout <= 128 && d->Cin <= 256 ? 1 : 0;
+  return d->Cout > 256;
 }
 
 int ssa_conv2d_gemm_wide(const ssa_conv_desc* dp, const void* x, const void* w_frag, const float* bias,

@@ -1,10 +1,10 @@
-// 3x3 convolutions of the OCR / attention heads, second geometry (gfx950 / MI355X): conv3x3_ocr 720->512 (28 % of the
-// step's FLOPs), the scale-attention head 512->256 / 256->256, and their data gradients (network/ocrnet.py:54-58,
-// network/utils.py:348-357; SURVEY.md K3).
+// 3x3 convolutions of the OCR / attention heads (gfx950 / MI355X): conv3x3_ocr 720->512 (28 % of the step's FLOPs),
+// the scale-attention head 512->256 / 256->256, and their data gradients (network/ocrnet.py:54-58,
+// network/utils.py:348-357; SURVEY.md K3-K4).
 //
-// conv_halo_gemm.hip's ConvHaloGemm3 gives a wave 64 pixels x 64 channels and streams the filter through an LDS ring:
-// every MFMA wants one ds_read_b128, every (chunk, tap) stage of 12-16 MFMAs per wave ends in a workgroup barrier,
-// and the kernel sits at 0.43-0.46 of the MFMA peak with `mfma_busy` 0.49-0.58 (profiles/r05_pmc.txt).  Here
+// A wave of 64 pixels x 64 channels with the filter streamed through an LDS ring wants one ds_read_b128 per MFMA and
+// ends every (chunk, tap) stage of 12-16 MFMAs per wave in a workgroup barrier: 0.43-0.46 of the MFMA peak with
+// `mfma_busy` 0.49-0.58 (profiles/r05_pmc.txt).  Here
 //   * a wave owns 128 pixels x 64 channels = 4 x 2 MFMA 32x32x16 tiles (128 accumulator registers): a 16-channel
 //     k-step is 4 A-fragment reads for 8 MFMAs -- half an LDS read per MFMA;
 //   * the FILTER NEVER TOUCHES LDS.  It lies in MFMA-fragment order [n-block][k-step][lane][8] (ssa_pack_filter mode
@@ -13,7 +13,7 @@
 //     clocks) ahead into the other half of a register double buffer; the compiler's own vmcnt bookkeeping orders them.
 //     The four waves of a workgroup own four DIFFERENT 64-channel slices, so no filter byte is fetched twice by a
 //     workgroup and nothing about the filter needs a barrier;
-//   * the input HALO tile (6 x 34 pixels of a CK-channel chunk, XOR-swizzled pixel-major image as in conv_halo_gemm.hip)
+//   * the input HALO tile (6 x 34 pixels of a CK-channel chunk, XOR-swizzled pixel-major image)
 //     arrives by LDS DMA, double buffered per chunk -- so the ONLY workgroup barrier of the main loop is the one per
 //     chunk: 216-288 MFMAs per wave between barriers instead of 12-16;
 //   * workgroup = 4 waves (1 x 4), tile 128 pixels (4 rows x 32) x 256 channels, 52 KiB of LDS for the pipeline: two

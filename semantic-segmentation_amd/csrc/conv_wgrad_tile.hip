@@ -23,9 +23,7 @@
 // grid.y partitions the output (co part, n part) so that a workgroup owns at
 // most 12 accumulator tiles per wave:
 //     C=48: 2 m-blocks x 14 n-blocks (all taps)      C=64: 2 x 18
-//     C=96: 3 x 9 (one kernel row kh per part)       C=192/384: the C=96 instantiation over
-//     (96 output channels) x (kernel row, 96 input channels) sub-problems -- 12 / 48 parts
-//     (SSA_WGRAD_C96=0: 6 x 6, one tap of 192 input x 192 output channels per part)
+// C=96/192/384 go to ConvWgradTileA (below) in (96 output x 96 input channel) blocks.
 #include "common.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
@@ -81,13 +79,9 @@ struct ConvWgradTile {
   const int n_part = by % n_parts, co_part = by / n_parts;
   const int co0 = co_part * MB * 32;
   const int Kflat = 9 * Cin;
-  // Column parts of dW[co][(tap, ci)].  CX = 96 ("row mode", Cin = 96 / 192 / 384): a part is one kernel
-  // row kh x one block of 96 input channels -- n-block nb = (kw = nb / 3, 32 channels (nb % 3) of the
-  // block) --, so the 192- and 384-channel layers run as 2x2 / 4x4 (co block, ci block) sub-problems of
-  // the 96-channel instantiation.  Otherwise a part is NBW*32 consecutive columns.
-  constexpr bool ROWS = CX == 96;
-  const int n0 = ROWS ? 0 : n_part * NBW * 32;
-  const int ci_base = ROWS ? (n_part / 3) * 96 : n0 % Cin;
+  // Column parts of dW[co][(tap, ci)]: a part is NBW*32 consecutive columns.
+  const int n0 = n_part * NBW * 32;
+  const int ci_base = n0 % Cin;
 
   // per-lane constants of the B (x) fragments of this wave's n-blocks
   const int li = lane & 15, lj = li >> 2, lq = li & 3, lg = (lane >> 4) & 1, lh = lane >> 5;
@@ -96,20 +90,13 @@ struct ConvWgradTile {
 #pragma unroll
   for (int l = 0; l < NBL; ++l) {
     const int nb = wave + 4 * l;
-    if constexpr (ROWS) {
-      const int kh = n_part % 3, kw = nb / 3, c32 = (nb - kw * 3) * 32;
-      const bool ok = nb < NBW;
-      b_off[l] = ok ? (kh * HW_ + kw) * SX + (c32 + 16 * lg + 4 * lq) * 2 : 0;
-      kcol0[l] = ok ? (kh * 3 + kw) * Cin + ci_base + c32 : -1;
-    } else {
-      const int n16 = n0 + nb * 32 + 16 * lg;
-      const bool ok = nb < NBW && n16 < Kflat;
-      const int tap = ok ? n16 / Cin : 0;
-      const int ci = ok ? n16 - tap * Cin - ci_base : -4 * lq;   // invalid: offset 0 (in bounds, discarded)
-      const int kh = tap / 3, kw = tap - kh * 3;
-      b_off[l] = (kh * HW_ + kw) * SX + (ci + 4 * lq) * 2;
-      kcol0[l] = nb < NBW ? n0 + nb * 32 : -1;
-    }
+    const int n16 = n0 + nb * 32 + 16 * lg;
+    const bool ok = nb < NBW && n16 < Kflat;
+    const int tap = ok ? n16 / Cin : 0;
+    const int ci = ok ? n16 - tap * Cin - ci_base : -4 * lq;   // invalid: offset 0 (in bounds, discarded)
+    const int kh = tap / 3, kw = tap - kh * 3;
+    b_off[l] = (kh * HW_ + kw) * SX + (ci + 4 * lq) * 2;
+    kcol0[l] = nb < NBW ? n0 + nb * 32 : -1;
   }
   const int a_col = (16 * lg + 4 * lq) * 2;     // byte offset of this lane's 4 channels inside an m-block
 
@@ -128,13 +115,10 @@ struct ConvWgradTile {
   constexpr int XI = (XN + 255) / 256, DI = (DN + 255) / 256;
   uint4 xv[XI], dv[DI];
   unsigned xmask = 0, dmask = 0;               // bit i = piece i lies inside the image
-  // tile-invariant part of every piece this thread moves: packed (row, column) inside the
+  // tile-invariant part of every piece this thread moves, kept in registers: packed (row, column) inside the
   // tile, element offset relative to the tile origin, LDS byte offset (-1: no such piece).
-  // Kept in registers when there are few pieces per thread (C <= 96); recomputed per tile
-  // for the 192-channel variant, whose accumulators leave no registers for them.
-  constexpr bool PRE = (XI + DI) <= 16;
-  int x_rc_[PRE ? XI : 1], x_go_[PRE ? XI : 1], x_lo_[PRE ? XI : 1];
-  int d_rc_[PRE ? DI : 1], d_go_[PRE ? DI : 1], d_lo_[PRE ? DI : 1];
+  int x_rc_[XI], x_go_[XI], x_lo_[XI];
+  int d_rc_[DI], d_go_[DI], d_lo_[DI];
   auto x_piece = [&](int i, int* rc, int* go, int* lo) {
     const int piece = tid + i * 256;
     const int pix = piece / XP, cp = piece - pix * XP;
@@ -151,12 +135,10 @@ struct ConvWgradTile {
     *go = (ty * W + tx) * lddy + cp * 8;
     *lo = (piece < DN && co0 + cp * 8 < cout_pad) ? pix * SD + cp * 16 : -1;
   };
-  if constexpr (PRE) {
 #pragma unroll
-    for (int i = 0; i < XI; ++i) x_piece(i, &x_rc_[i], &x_go_[i], &x_lo_[i]);
+  for (int i = 0; i < XI; ++i) x_piece(i, &x_rc_[i], &x_go_[i], &x_lo_[i]);
 #pragma unroll
-    for (int i = 0; i < DI; ++i) d_piece(i, &d_rc_[i], &d_go_[i], &d_lo_[i]);
-  }
+  for (int i = 0; i < DI; ++i) d_piece(i, &d_rc_[i], &d_go_[i], &d_lo_[i]);
   // global -> registers for tile t (x halo image, zero outside the image; dy tile, zero
   // outside the image / past cout_pad); issued one tile ahead of the MFMAs
   auto fetch = [&](int t) {
@@ -173,8 +155,7 @@ struct ConvWgradTile {
     xmask = 0;
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
-      int rc, go, lo;
-      if constexpr (PRE) { rc = x_rc_[i]; go = x_go_[i]; lo = x_lo_[i]; } else { x_piece(i, &rc, &go, &lo); }
+      const int rc = x_rc_[i], go = x_go_[i], lo = x_lo_[i];
       const int iy = y0 - 1 + (rc >> 8), ix = x0 - 1 + (rc & 255);
       const bool ok = lo >= 0 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
       xv[i] = *reinterpret_cast<const uint4*>(xb + (ok ? go : (W + 1) * ldx));
@@ -183,8 +164,7 @@ struct ConvWgradTile {
     dmask = 0;
 #pragma unroll
     for (int i = 0; i < DI; ++i) {
-      int rc, go, lo;
-      if constexpr (PRE) { rc = d_rc_[i]; go = d_go_[i]; lo = d_lo_[i]; } else { d_piece(i, &rc, &go, &lo); }
+      const int rc = d_rc_[i], go = d_go_[i], lo = d_lo_[i];
       const bool ok = lo >= 0 && y0 + (rc >> 8) < H && x0 + (rc & 255) < W;
       dv[i] = *reinterpret_cast<const uint4*>(db + (ok ? go : 0));
       dmask |= (ok ? 1u : 0u) << i;
@@ -193,8 +173,7 @@ struct ConvWgradTile {
   auto stage = [&]() {
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
-      int lo;
-      if constexpr (PRE) { lo = x_lo_[i]; } else { int rc, go; x_piece(i, &rc, &go, &lo); }
+      const int lo = x_lo_[i];
       if (lo >= 0) *reinterpret_cast<uint4*>(Xs + lo) = ((xmask >> i) & 1u) ? xv[i] : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
@@ -227,28 +206,19 @@ struct ConvWgradTile {
 #pragma unroll
         for (int l = 0; l < NL; ++l) bfr[slot][l] = tr_read8(Xs + (ty * HW_ + kp) * SX + b_off[l], SX);
       };
-      constexpr bool PIPE = CX != 192;          // the 192-channel instantiation has no registers for a second set
-      if constexpr (PIPE) {
-        rd(0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MB + NL), 0);    // the prologue reads are a group of their own
-      }
+      rd(0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MB + NL), 0);    // the prologue reads are a group of their own
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) {
-        if constexpr (PIPE) {
-          if (ks + 1 < 8) rd(ks + 1, (ks + 1) & 1);
-        } else {
-          rd(ks, 0);
-        }
-        const int slot = PIPE ? (ks & 1) : 0;
+        if (ks + 1 < 8) rd(ks + 1, (ks + 1) & 1);
+        const int slot = ks & 1;
 #pragma unroll
         for (int l = 0; l < NL; ++l)
 #pragma unroll
           for (int mb = 0; mb < MB; ++mb)
             acc[mb][l] = ssa_mfma32(af[slot][mb], bfr[slot][l], acc[mb][l]);
-        if constexpr (PIPE) {
-          if (ks + 1 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MB + NL), 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, MB * NL, 0);
-        }
+        if (ks + 1 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MB + NL), 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, MB * NL, 0);
       }
     };
     constexpr int NL_LO = NBW / 4, NL_HI = (NBW + 3) / 4;      // n-blocks of waves >= NBW % 4 / of the others
@@ -274,10 +244,10 @@ struct ConvWgradTile {
 };
 
 // ---- All nine taps per staged tile, LDS-DMA double buffer (round 6) ----------------------------------------------------
-// ConvWgradTile above holds 9 accumulator tiles per wave AND the next tile's x / dy pieces in registers (it stages
-// through them) AND their addresses: 467 registers per lane, i.e. ONE 4-wave workgroup per CU (the host sized its
-// launches for two), whose single wave per SIMD alternates between staging, two barriers and 48-72 MFMAs per tile --
-// MFMA pipe busy 0.12 (profiles/r05_pmc.txt); and a 96-channel block's tile is staged three times, once per kernel row.
+// ConvWgradTile above holds its accumulator tiles AND the next tile's x / dy pieces in registers (it stages through
+// them) AND their addresses: for a 96-channel block (9 tiles per wave, one kernel row per workgroup) that is 467
+// registers per lane, i.e. ONE 4-wave workgroup per CU, whose single wave per SIMD alternates between staging, two
+// barriers and 48-72 MFMAs per tile -- MFMA pipe busy 0.12 (profiles/r05_pmc.txt) -- and a tile staged three times.
 // Here, for the 96-channel blocks (Cin = Cout = 96 / 192 / 384: three quarters of the trunk's weight-gradient FLOPs),
 //   * a workgroup (4 waves, one per SIMD) owns HALF of the 27 (tap, 32-channel) n-blocks -- 14 or 13 -- x 3 m-blocks of
 //     its (96 co x 96 ci) block: wave w holds n-blocks w, w + 4, w + 8, w + 12 of its half x 3 m-blocks = 12
@@ -456,29 +426,14 @@ struct ConvWgradTileA {
 
 struct Plan { int cx, mb, nbw, n_parts, co_parts; };
 
-bool c96_on() {
-  static const bool on = !(getenv("SSA_WGRAD_C96") && atoi(getenv("SSA_WGRAD_C96")) == 0);
-  return on;
-}
-
-// SSA_WGRAD_ALL=0: the 96-channel blocks stay on the 4-wave, one-kernel-row-per-workgroup form
-bool all_taps_on() {
-  static const bool on = !(getenv("SSA_WGRAD_ALL") && atoi(getenv("SSA_WGRAD_ALL")) == 0);
-  return on;
-}
-
 bool make_plan(int Cin, int cout_pad, Plan* p) {
   if (Cin != cout_pad) return false;
-  if (all_taps_on() && (Cin == 96 || Cin == 192 || Cin == 384)) {      // ConvWgradTileA: cx = 0 marks it
-    *p = Plan{0, 3, 27, 2 * (Cin / 96), Cin / 96};       // n_parts = 2 halves of the n-blocks x ci blocks
-    return true;
-  }
   switch (Cin) {
     case 48: *p = {48, 2, 14, 1, 1}; return true;
     case 64: *p = {64, 2, 18, 1, 1}; return true;
-    case 96: *p = {96, 3, 9, 3, 1}; return true;
-    case 192: *p = c96_on() ? Plan{96, 3, 9, 6, 2} : Plan{192, 6, 6, 9, 1}; return true;
-    case 384: *p = c96_on() ? Plan{96, 3, 9, 12, 4} : Plan{192, 6, 6, 18, 2}; return true;
+    case 96: case 192: case 384:                         // ConvWgradTileA: cx = 0 marks it
+      *p = Plan{0, 3, 27, 2 * (Cin / 96), Cin / 96};     // n_parts = 2 halves of the n-blocks x ci blocks
+      return true;
     default: return false;
   }
 }
@@ -534,13 +489,14 @@ int ssa_conv2d_wgrad_tile_plan(const ssa_conv_desc* d, int cout_pad, int* nsplit
 
 // What the host's launch planning needs to know about a layer's launch: workgroups per strip (`parts`) and how many
 // workgroups of this instantiation the chip holds at once (`slots`: 64 KB of LDS and <= 256 registers x 4 waves = two per
-// CU on paper -- the 4-wave form in fact holds 467 registers and gets ONE; the 8-wave all-taps form: one per CU).
+// CU on paper -- the 4-wave forms in fact hold 384 / 465 registers (48 / 64 channels) and get ONE; the all-taps form:
+// one per CU).
 int ssa_conv2d_wgrad_tile_geometry(int Cin, int cout_pad, int* parts, int* slots, int* kind) {
   Plan p;
   if (!parts || !slots || !kind || !make_plan(Cin, cout_pad, &p)) return SSA_EUNSUPPORTED;
   *parts = p.n_parts * p.co_parts;
   *slots = 256;
-  *kind = p.cx == 0 ? 0 : (p.cx == 96 ? 96 : p.cx);      // launches group by instantiation
+  *kind = p.cx;                                          // launches group by instantiation
   return SSA_OK;
 }
 
@@ -562,14 +518,8 @@ int ssa_conv2d_wgrad_tile(const ssa_conv_desc* dp, const void* x, const void* dy
     a.tiles_x = (d.W + 31) / 32; a.tiles_y = (d.H + 3) / 4; a.tiles_per_wg = tpw; a.n_parts = p.n_parts;
     return ssa::submit<K>(a, nsplit, p.n_parts * p.co_parts, K::LDS_BYTES, s);
   }
-  switch (d.Cin) {
-    case 48: return launch<48, 2, 14>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
-    case 64: return launch<64, 2, 18>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
-    case 96: return launch<96, 3, 9>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
-    default:
-      if (p.cx == 96) return launch<96, 3, 9>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
-      return launch<192, 6, 6>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
-  }
+  if (d.Cin == 48) return launch<48, 2, 14>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
+  return launch<64, 2, 18>(d, p, x, dy, lddy, cout_pad, nsplit, tpw, partial, s);
 }
 
 }  // extern "C"

@@ -136,11 +136,6 @@ _SIGS = {
     "ssa_p2p_vmm_alloc": ([c_size_t, POINTER(c_void_p), POINTER(c_int), POINTER(c_size_t)], c_int),
     "ssa_p2p_vmm_import": ([c_int, c_size_t, POINTER(c_void_p)], c_int),
     "ssa_p2p_vmm_unmap": ([_P, c_size_t], c_int),
-    "ssa_bn_bwd_fused_blocks": ([c_long, c_int], c_int),
-    "ssa_bn_bwd_fused_capacity": ([], c_int),
-    "ssa_bn_bwd_fused_timeouts": ([_P], c_int),
-    "ssa_bn_bwd_fused": ([_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_long, c_int,
-                          _P, _P, _P, _P, c_int, c_double, c_int, _P, c_long, _P, _P, c_float, _P, _P, c_int, _P, _P, _P], c_int),
     "ssa_sum_act": ([_P, _P, _P, _P, _P, c_long, c_int, _P], c_int),
     "ssa_relu_bwd": ([_P, _P, _P, c_long, _P], c_int),
     "ssa_nchw_f32_to_nhwc_bf16": ([_P, _P, c_int, c_int, c_int, c_int, c_int, _P], c_int),

@@ -156,7 +156,6 @@ _PACK_TILED = os.environ.get("SSA_PACK_TILED", "1") != "0"
 
 
 def clear_pack_cache():
-    join_pack()
     _PACKED.clear()
     _JOB_TABLES.clear()
 
@@ -197,23 +196,7 @@ def _make_job(w, out, Cout, Cin, KH, KW, cin_pad, cout_pad, Kpad, mode, rows, la
     return PackJob(w.data_ptr(), out.data_ptr(), 0, Cout, Cin, KH, KW, cin_pad, cout_pad, Kpad, mode, rows, layout)
 
 
-# The re-pack of a training step (288 MB of fp32 parameters -> their 16-bit operand forms, ~0.2 ms, HBM-bound) is the
-# first thing of the step and only the stem's filters are needed at once: begin_step packs the first SSA_PACK_EARLY
-# filters (registration order = order of first use) on the compute stream and the rest on a stream of its own, next to
-# the stem and layer1 (~0.7 ms of 10-30 us launches); the first conv that asks for one of the late filters makes the
-# compute stream wait (_packed_filter).  SSA_PACK_EARLY=0 (the default): one launch on the compute stream -- measured
-# with 20: 20.19 / 20.46 / 20.38 against 20.41 ms per step, nothing gained (profiles/r06_notes.md call S).
-_PACK_EARLY = int(os.environ.get("SSA_PACK_EARLY", "0"))
-_PACK_SIDE = {"stream": None, "pending": False, "late": frozenset()}
 _JOB_TABLES = {}
-
-
-def join_pack():
-    """The current stream waits for the filters being packed on the side stream."""
-    if _PACK_SIDE["pending"]:
-        torch.cuda.current_stream().wait_stream(_PACK_SIDE["stream"])
-        _PACK_SIDE["pending"] = False
-        _PACK_SIDE["late"] = frozenset()
 
 
 def _pack_launch(stale):
@@ -241,11 +224,9 @@ def _pack_launch(stale):
               "ssa_pack_filters_batched")
 
 
-def refresh_packed_filters(overlap=False):
+def refresh_packed_filters():
     """Re-pack every registered filter whose parameter changed since it was
-    packed.  One launch for all of them; overlap=True (begin_step: host code asks for every filter before its conv is
-    launched): two launches, the second on a side stream (above)."""
-    join_pack()
+    packed.  One launch for all of them."""
     stale = []
     for key, e in list(_PACKED.items()):
         w = e.wref()
@@ -256,19 +237,7 @@ def refresh_packed_filters(overlap=False):
             stale.append((key, e, w))
     if not stale:
         return
-    if overlap and 0 < _PACK_EARLY < len(stale) and stale[0][2].is_cuda:
-        early, late = stale[:_PACK_EARLY], stale[_PACK_EARLY:]
-        _pack_launch(early)
-        if _PACK_SIDE["stream"] is None:
-            _PACK_SIDE["stream"] = torch.cuda.Stream()
-        side = _PACK_SIDE["stream"]
-        side.wait_stream(torch.cuda.current_stream())         # the optimizer's update of the parameters
-        with torch.cuda.stream(side):
-            _pack_launch(late)
-        _PACK_SIDE["pending"] = True
-        _PACK_SIDE["late"] = frozenset(k for k, _, _ in late)
-    else:
-        _pack_launch(stale)
+    _pack_launch(stale)
     for _, e, w in stale:
         e.version = w._version
 
@@ -277,8 +246,6 @@ def _packed_filter(weight, mode, cin_pad, cout_pad):
     key = (weight.data_ptr(), mode, cin_pad, cout_pad)
     e = _PACKED.get(key)
     if e is not None and e.wref() is not None and e.version == weight._version and e.shape == tuple(weight.shape):
-        if _PACK_SIDE["pending"] and key in _PACK_SIDE["late"]:
-            join_pack()
         return e.out, e.Kpad
     Cout, Cin, KH, KW = weight.shape
     layout = 0                  # one fragment order (reserved field of ssa_pack_job)
@@ -489,7 +456,7 @@ def begin_step(device=None):
         # stay "armed" (or keep stale slots) and no later backward pass would ever publish a gradient again
         del _WGRAD_Q[:]
         _GRADS.abandon()
-    refresh_packed_filters(overlap=True)
+    refresh_packed_filters()
     if device is not None:
         _ARENA.reset(device)
 
@@ -1394,34 +1361,6 @@ def _bn_train_fwd(xs, ldxs, metas, gammas, betas, ress, posts, masks=None):
     return zs, coefs, counts, worlds
 
 
-# OFF by default: measured (round 6, calls P / P2, tools/bnbench.py) 49 us for a 7.4 M-element level against 8.3 + 14.0 us
-# for the two launches -- the rendezvous of ~930 workgroups across 8 XCDs (one returning atomic per workgroup on one
-# address + the polls, all served at the memory-side coherence point) costs more than the second read of (x, dz, mask)
-# it saves, which comes from the 256 MB MALL anyway.  SSA_BN_FUSED_BWD=1 switches it on; the kernel and its test stay.
-_BN_FUSED_BWD = os.environ.get("SSA_BN_FUSED_BWD", "0") == "1"
-
-
-def _bn_bwd_fused_ids(todo):
-    """ids of the jobs of `todo` that take the one-launch backward: training-mode, no SyncBN exchange, one chunk per
-    workgroup, and all of them together within the chip's resident-workgroup capacity (the rendezvous inside the kernel
-    waits for every workgroup of a problem)."""
-    if not _BN_FUSED_BWD or not todo:
-        return set()
-    L = lib()
-    cap = L.ssa_bn_bwd_fused_capacity()
-    total, ids = 0, set()
-    for j in todo:
-        B, H, W, C = j["x"].shape
-        nb = L.ssa_bn_bwd_fused_blocks(B * H * W, C) if (j["training"] and not j["world"]) else 0
-        if nb <= 0:
-            continue
-        if total + nb > cap:
-            return set()            # (a bracket that does not fit stays on the two-launch form as a whole)
-        total += nb
-        ids.add(id(j))
-    return ids
-
-
 def _bn_bwd(jobs):
     """Backward of N BatchNorm(+ReLU/residual/mask) problems.  job: dict with x, ldx, dz, lddz, z,
     coef, g (gamma fp32 or None), gamma_param, beta_param, relu, pst, training, world, count,
@@ -1436,11 +1375,6 @@ def _bn_bwd(jobs):
         if j.get("sums") is None:
             j["sums"] = _ARENA.take(j["nrep"] * 2 * C, j["x"].device)
             todo.append(j)
-    # the jobs whose sums nobody has formed yet go through ONE launch (reduce, grid-wide rendezvous, apply: the chunk
-    # stays in registers, csrc/bn.hip bn_bwd_fused_body) when every workgroup of the bracket fits on the chip at once
-    # and no SyncBN exchange has to happen between the two halves
-    fused = _bn_bwd_fused_ids(todo)
-    todo = [j for j in todo if id(j) not in fused]
     if todo:
         with group():
             for j in todo:
@@ -1494,15 +1428,6 @@ def _bn_bwd(jobs):
             dx = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev)
             dres = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev) if j["has_res"] else None
             _note(0.0, 2.0 * P * C * (3 + (1 if dres is not None else 0)))
-            if id(j) in fused:
-                ticket = _ARENA.take(1, dev)
-                check(L.ssa_bn_bwd_fused(_p(x), j["ldx"], _p(j["dz"]), j["lddz"], _p(j["z"]), C, _p(dx), C, _p(dres), C, P, C,
-                                         _p(g), _p(coef[2]), _p(coef[3]), _p(use_sums), j["nrep"], j["count"], int(j["relu"]),
-                                         _p(j["pst"]), H * W, _p(pg_g) if fuse_pg else None, _p(pg_b) if fuse_pg else None,
-                                         pscale, _p(msc), _p(msh), accumulate if fuse_pg else 0, _p(j.get("mask")),
-                                         _p(ticket), _s()), "ssa_bn_bwd_fused")
-                out.append((dx, dres, ret_g, ret_b))
-                continue
             check(L.ssa_bn_bwd_apply(_p(x), j["ldx"], _p(j["dz"]), j["lddz"], _p(j["z"]), C, _p(dx), C, _p(dres), C, P, C,
                                      _p(g), _p(coef[2]), _p(coef[3]), _p(use_sums), j["nrep"], j["count"], int(j["relu"]),
                                      _p(j["pst"]), H * W, _p(pg_g) if fuse_pg else None, _p(pg_b) if fuse_pg else None,

@@ -122,7 +122,8 @@ CONV_CASES = [
     (1, 33, 30, 192, 96, 3, 1, 1, 1, False, False),
     (2, 20, 12, 384, 200, 3, 1, 1, 1, True, False),
     (1, 64, 64, 192, 192, 3, 1, 1, 1, False, False),
-    # halo-chunk GEMM (conv_halo_gemm.hip): CK 48 / 64, 3x3 / 1x1, ragged tiles, partial n-blocks
+    # large-channel head convs (ssa_conv2d_halo): 3x3 on ConvHaloReg3, 1x1 on ConvHaloGemm1; CK 48 / 64, ragged tiles,
+    # partial n-blocks
     (1, 130, 131, 192, 200, 3, 1, 1, 1, True, False),
     (1, 128, 129, 240, 128, 3, 1, 1, 1, False, False),
     (2, 96, 100, 256, 72, 1, 1, 0, 1, False, False),
@@ -498,32 +499,19 @@ def test_batched_filter_repack():
     assert tab["tiles"] is not None and 300 < tab["ntiles"] < 600   # the tile-balanced kernel ran, ONE tile list per
     # source tensor: the 25 operand forms of the 8 tensors are chained (600+ tiles if every form fetched its own)
     batched = [t.clone() for t in first]       # same persistent buffers, refreshed in place
-    # ... and the step's form: the first filters on this stream, the rest on a side stream, joined by the first lookup
-    # of a late filter (begin_step -> refresh_packed_filters(overlap=True)); same bits as the one-launch form
     saved = [w.clone() for w in ws]
     for w in ws:
         w.mul_(2.0).sub_(0.125)
-    early = hb._PACK_EARLY
-    hb._PACK_EARLY = 5
-    try:
-        hb.refresh_packed_filters(overlap=True)
-        if ws[0].is_cuda:                                        # (the CPU emulation has no second stream: one launch)
-            assert hb._PACK_SIDE["pending"] and len(hb._PACK_SIDE["late"]) == len(specs) - 5
-            hb._packed_filter(ws[owners[2]], *specs[2])
-            assert hb._PACK_SIDE["pending"]                      # an early filter: nothing to wait for
-            hb._packed_filter(ws[owners[-1]], *specs[-1])
-            assert not hb._PACK_SIDE["pending"]                  # a late one: the compute stream waits
-    finally:
-        hb._PACK_EARLY = early
+    hb.refresh_packed_filters()
     torch.cuda.synchronize()
-    split = [t.clone() for t in first]
+    updated = [t.clone() for t in first]
     for w in ws:
         w.add_(0.0)                                          # version bump only
     hb.refresh_packed_filters()
     torch.cuda.synchronize()
-    for o, sp, got, one in zip(owners, specs, split, first):
-        assert torch.equal(got.view(torch.int16), one.view(torch.int16)), ("two launches vs one", o, sp)
-    assert any(not torch.equal(a.view(torch.int16), b.view(torch.int16)) for a, b in zip(split, batched))
+    for o, sp, got, one in zip(owners, specs, updated, first):
+        assert torch.equal(got.view(torch.int16), one.view(torch.int16)), ("re-pack of unchanged weights", o, sp)
+    assert any(not torch.equal(a.view(torch.int16), b.view(torch.int16)) for a, b in zip(updated, batched))
     for w, w1 in zip(ws, saved):
         w.copy_(w1)
     hb.refresh_packed_filters()
@@ -603,62 +591,6 @@ def test_bn_train(C, relu, res, post):
     check_close("bn_dbeta", bd.grad, br.grad, 1e-2, 4e-3)
     if res:
         check_close("bn_dres", nchw(rd.grad.float()), rr.grad)
-
-
-@pytest.mark.parametrize("C,res,level", [(48, True, False), (96, False, False), (48, True, True)])
-def test_bn_bwd_fused_equals_two_launches(C, res, level):
-    """The one-launch BatchNorm backward (reduce, grid-wide rendezvous, apply: csrc/bn.hip bn_bwd_fused_body) against
-    the two-launch form on the same inputs: the sums are formed by the same per-workgroup partials in another order of
-    fp64 atomics, so everything agrees to fp32 rounding of the coefficients (1e-5 relative; the 16-bit outputs then differ
-    in at most the last bit); no workgroup may have timed out of the rendezvous.  `level`: several problems in one grouped
-    launch, each with its own ticket."""
-    import ctypes
-    hb = _hb()
-    if DEV != "cuda":
-        pytest.skip("the rendezvous needs concurrently resident workgroups: not on the CPU emulation")
-    shapes = [(1, 40, 56, C)] if not level else [(1, 64, 64, C), (1, 32, 32, 2 * C), (1, 16, 16, 4 * C)]
-
-    def run(fused_on):
-        prev = hb._BN_FUSED_BWD
-        hb._BN_FUSED_BWD = fused_on
-        try:
-            outs = []
-            xs, gs, bs, rs, zs = [], [], [], [], []
-            for k, (B, H, W, c) in enumerate(shapes):
-                x = _to_dev_nhwc(_rand(B, c, H, W, seed=10 + k) * 1.3 + 0.2).requires_grad_(True)
-                g = (torch.rand(c, generator=torch.Generator().manual_seed(20 + k)) + 0.5).to(DEV).requires_grad_(True)
-                b = (torch.randn(c, generator=torch.Generator().manual_seed(30 + k)) * 0.1).to(DEV).requires_grad_(True)
-                r = _to_dev_nhwc(_rand(B, c, H, W, seed=40 + k)).requires_grad_(True) if res else None
-                xs.append(x); gs.append(g); bs.append(b); rs.append(r)
-            for k, (B, H, W, c) in enumerate(shapes):
-                rm, rv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
-                nbt = torch.zeros((), dtype=torch.long, device=DEV)
-                zs.append(hb.BatchNormActFn.apply(xs[k], gs[k], bs[k], rs[k], None, rm, rv, nbt, 0.1, 1e-5, True, True, False, None))
-            tot = sum((z.float() * nhwc(_rand(*[z.shape[0], z.shape[3], z.shape[1], z.shape[2]], seed=50 + k)).to(DEV)).sum()
-                      for k, z in enumerate(zs))
-            tot.backward()
-            torch.cuda.synchronize()
-            for k in range(len(shapes)):
-                outs.append((xs[k].grad.float().cpu(), gs[k].grad.cpu(), bs[k].grad.cpu(), rs[k].grad.float().cpu() if res else None))
-            return outs
-        finally:
-            hb._BN_FUSED_BWD = prev
-
-    L = hb.lib()
-    t0 = ctypes.c_uint(0)
-    assert L.ssa_bn_bwd_fused_timeouts(ctypes.byref(t0)) == 0
-    two = run(False)
-    one = run(True)
-    t1 = ctypes.c_uint(0)
-    assert L.ssa_bn_bwd_fused_timeouts(ctypes.byref(t1)) == 0
-    assert t1.value == t0.value, "workgroups timed out of the rendezvous: %d" % (t1.value - t0.value)
-    assert L.ssa_bn_bwd_fused_capacity() >= 256
-    for (dx2, dg2, db2, dr2), (dx1, dg1, db1, dr1) in zip(two, one):
-        check_close("fused dx", dx1, dx2, 1.6e-2, 1e-4)          # one 16-bit ulp
-        check_close("fused dgamma", dg1, dg2, 1e-5, 1e-5)
-        check_close("fused dbeta", db1, db2, 1e-5, 1e-5)
-        if res:
-            assert torch.equal(dr1, dr2)
 
 
 def test_bn_deferred_running_stats_two_passes():
