@@ -652,6 +652,29 @@ int ssa_resample_u8(const unsigned char* src, int Hs, int Ws, int C, int axis, u
 int ssa_confusion_matrix(const float* logits, int ld, const int64_t* labels, long P, int C,
                          unsigned char* pred_out, int64_t* hist, void* stream);
 
+/* The whole tail of eval_minibatch in one launch (utils/trnval_utils.py:116-196, utils/misc.py:50-67,
+ * loss/utils.py:121-134; csrc/eval_tail.hip).  With the reference's statement order:
+ *     out[p,c] = 0.0f;  for s in 0 .. n_src-1:  out[p,c] = out[p,c] + src_s[flips[s] ? mirror_w(p) : p, c]
+ *     out[p,c] = (out[p,c] / div_scales) / div_flips                 two IEEE fp32 divisions, in this order
+ *     m = max_c out[p,c];  arg = first c with out[p,c] == m  (a NaN wins once, as in ssa_confusion_matrix)
+ *     se = sum_c exp(out[p,c] - m)
+ *     pred[p] = arg                                   uint8 [P]            optional
+ *     prob[p] = 1 / se  (= max_c softmax(out)[p])     fp32  [P]            optional
+ *     err[p]  = gt >= 0 && gt != ignore_label && arg != gt    uint8 [P]    optional, needs labels
+ *     hist[gt*C + arg] += 1  for 0 <= gt < C          int64 [C*C], ACCUMULATED   optional, needs labels
+ *     loss_acc[0] += (m + log se) - out[p,gt];  loss_acc[1] += 1   for gt != ignore_label && 0 <= gt < C
+ *                                                     double[2], ACCUMULATED (CrossEntropyLoss2d = [0] / [1])
+ *     avg[p,c] = out[p,c]                             fp32 dense [P,C]     optional
+ * srcs / flips: HOST arrays of n_src (1 .. 8) entries: device pointers to fp32 NHWC tensors [B,H,W,C] of common pixel
+ * stride ld >= C, and "mirrored along W" flags (mirror_w(b,y,x) = (b,y,W-1-x): the flip is an index, never a tensor).
+ * The pointers travel as kernel arguments.  labels int64 [B,H,W] or NULL.  1 <= C <= 128.  SSA_EINVAL (before the
+ * device is touched) for anything else, for a null source, for an output that needs labels without labels and when
+ * no output is asked for.                                                                                      */
+int ssa_eval_tail(const float* const* srcs, const int* flips, int n_src, int ld, int B, int H, int W, int C,
+                  const int64_t* labels, int ignore_label, float div_scales, float div_flips,
+                  unsigned char* pred, float* prob, unsigned char* err, int64_t* hist, double* loss_acc,
+                  float* avg, void* stream);
+
 /* Optimizer step (train.py:509 on the torch.optim.SGD of loss/optimizer.py:47-53;
  * SURVEY.md 8f rank 3): for every tensor i, elementwise in fp32
  *     d = g + weight_decay*p;  buf = momentum*buf + d;  p -= lr * (nesterov ? d + momentum*buf : buf)

@@ -225,4 +225,21 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Two fp64 partial sums of a workgroup of NT threads -> acc[0], acc[1]: wave shuffles, one LDS round, two atomics
+// (the {sum, count} pair of the pixel losses and of the evaluation tail).  Every thread of the workgroup calls it.
+template <int NT> __device__ __forceinline__ void ssa_block_acc2(double a, double b, double* acc) {
+  __shared__ double red[2 * (NT / 64)];
+  a = wave_sum_d(a);
+  b = wave_sum_d(b);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { red[2 * w] = a; red[2 * w + 1] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sa = 0, sb = 0;
+    for (int i = 0; i < NT / 64; ++i) { sa += red[2 * i]; sb += red[2 * i + 1]; }
+    atomicAdd(&acc[0], sa);
+    atomicAdd(&acc[1], sb);
+  }
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }

@@ -17,21 +17,6 @@ constexpr int NT = 256;
 constexpr float kClipMin = 1e-6f;   // loss/rmi.py:24  _CLIP_MIN
 constexpr double kPosAlpha = 5e-4;  // loss/rmi.py:26  _POS_ALPHA
 
-__device__ __forceinline__ void block_acc2(double a, double b, double* acc) {
-  __shared__ double red[2 * (NT / 64)];
-  a = wave_sum_d(a);
-  b = wave_sum_d(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red[2 * w] = a; red[2 * w + 1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double sa = 0, sb = 0;
-    for (int i = 0; i < NT / 64; ++i) { sa += red[2 * i]; sb += red[2 * i + 1]; }
-    atomicAdd(&acc[0], sa);
-    atomicAdd(&acc[1], sb);
-  }
-}
-
 // MODE 0: softmax cross entropy;  MODE 1: masked sigmoid BCE (sum over classes)
 template <int MODE>
 __global__ __launch_bounds__(NT) void pixel_loss_kernel(const float* __restrict__ logits, int ld,
@@ -88,7 +73,7 @@ __global__ __launch_bounds__(NT) void pixel_loss_kernel(const float* __restrict_
     }
     __syncthreads();
   }
-  block_acc2(lsum, lcnt, acc);
+  ssa_block_acc2<NT>(lsum, lcnt, acc);
 }
 
 // Masked sigmoid BCE, dense logits: nothing couples the classes of a pixel, so the tile kernel's stage-in / per-pixel
@@ -146,7 +131,7 @@ __global__ __launch_bounds__(NT) void bce_stream_kernel(const float* __restrict_
     for (int u = 0; u < 4; ++u)
       if (u == 0 || g0 + u * stride < n4) element(gi[u], v[u], pi[u], l0[u], l1[u]);
   }
-  block_acc2(lsum, lcnt, acc);
+  ssa_block_acc2<NT>(lsum, lcnt, acc);
 }
 
 // Backward of the dense masked BCE without a saved gradient: d = (sigmoid(v) - onehot) * upstream * coef / count for

@@ -23,6 +23,7 @@ def _defaults():
     c.MODEL = AttrDict(
         BNFUNC=None,                 # config.py:216-225 picks the norm layer; None -> semseg_amd.nn.BatchNorm2d
         ALIGN_CORNERS=False,         # config.py:125
+        MSCALE=False,                # config.py:122; assert_and_infer_cfg sets it for the mscale / attnscale architectures
         MSCALE_LO_SCALE=0.5,         # config.py:126
         N_SCALES=None,               # config.py:124
         SEGATTN_BOT_CH=256,          # config.py:130
@@ -51,7 +52,7 @@ cfg = _defaults()
 def sync_from_reference(ref_cfg):
     """Copy the fields the hot path reads from the reference's global cfg."""
     m = ref_cfg.MODEL
-    for k in ("ALIGN_CORNERS", "MSCALE_LO_SCALE", "N_SCALES", "SEGATTN_BOT_CH", "ASPP_BOT_CH", "MSCALE_INNER_3x3",
+    for k in ("ALIGN_CORNERS", "MSCALE", "MSCALE_LO_SCALE", "N_SCALES", "SEGATTN_BOT_CH", "ASPP_BOT_CH", "MSCALE_INNER_3x3",
               "HRNET_CHECKPOINT"):
         if hasattr(m, k):
             cfg.MODEL[k] = getattr(m, k)

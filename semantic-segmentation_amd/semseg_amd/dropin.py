@@ -11,6 +11,9 @@ time, so `train.py`, `config.py` and `scripts/*.yml` run unchanged:
   loss.utils (get_loss, CrossEntropyLoss2d), loss.rmi (RMILoss), loss.optimizer (get_optimizer,
   restore_opt, restore_net, ...)
         -> semseg_amd.loss.*         (train.py:45-46,341,378)
+  utils.trnval_utils (eval_minibatch, flip_tensor, resize_tensor; validate_topn raises) -- only with
+  install(device_eval_tail=True)
+        -> semseg_amd.utils.eval_tail    (train.py:44; the evaluation tail in one kernel instead of on the host)
   apex.parallel.SyncBatchNorm / DistributedDataParallel, apex.amp
         -> semseg_amd.nn.SyncBatchNorm / semseg_amd.parallel.DistributedDataParallel /
            semseg_amd.amp behind apex.amp's names: `--fp16` selects the fp16-storage build of the library and
@@ -74,7 +77,9 @@ def _select_storage_from_argv():
         os.environ["SSA_ACT_DTYPE"] = "fp16"
 
 
-def install(replace_apex=True):
+def install(replace_apex=True, device_eval_tail=False):
+    """device_eval_tail=True also registers `utils.trnval_utils` (train.py:44 imports eval_minibatch and validate_topn
+    from there): eval_minibatch with its tail on the device (semseg_amd/utils/eval_tail.py).  Off by default."""
     _select_storage_from_argv()
     from . import nn as snn, parallel, network, loss
     from .network import ocrnet, hrnetv2, ocr_utils, utils as nutils, mynn, deepv3, mscale, mscale2, attnscale
@@ -106,6 +111,15 @@ def install(replace_apex=True):
                       ("network.mscale2", mscale2), ("network.attnscale", attnscale),
                       ("loss.utils", criteria), ("loss.rmi", criteria), ("loss.optimizer", optimizer)):
         sys.modules[name] = mod
+    if device_eval_tail:
+        import importlib
+        et = importlib.import_module(__package__ + ".utils.eval_tail")     # (the package re-exports a function of that name)
+        tv = types.ModuleType("utils.trnval_utils")
+        tv.__doc__ = "utils/trnval_utils.py with the tail of eval_minibatch on the device (semseg_amd.utils.eval_tail)"
+        for fname in ("eval_minibatch", "flip_tensor", "resize_tensor", "validate_topn"):
+            setattr(tv, fname, getattr(et, fname))
+        et._SYNC_CFG[0] = True
+        sys.modules["utils.trnval_utils"] = tv
     return network, loss
 
 

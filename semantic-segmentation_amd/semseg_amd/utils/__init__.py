@@ -1,2 +1,3 @@
 """Device-side pieces of the reference's evaluation loop (utils/trnval_utils.py, utils/misc.py)."""
-from .eval_tail import confusion_matrix, fast_hist   # noqa: F401
+from .eval_tail import (confusion_matrix, fast_hist, eval_tail, eval_minibatch, flip_tensor,   # noqa: F401
+                        resize_tensor, validate_topn, EvalTailResult)
