@@ -708,6 +708,34 @@ int ssa_amp_update(float* amp_state, int growth_interval, float growth, float ba
 int ssa_amp_update_counted(float* amp_state, float* counters, int growth_interval, float growth, float backoff,
                            float min_scale, float max_scale, void* stream);
 
+/* Adam, AMSGrad and RAdam (train.py:509 `optim.step()` on the torch.optim.Adam of loss/optimizer.py:55-59, mode 0, with
+ * `--amsgrad` mode 1, or on the RAdam of loss/optimizer.py:60-63 = loss/radam.py:29-107, mode 2), the siblings of
+ * ssa_sgd_momentum_step: HOST arrays of n_tensors device pointers to dense fp32 tensors, up to 56 tensors per launch,
+ * the pointers travel as kernel arguments.  Whatever depends on the step count lives in a 16-byte device record per
+ * parameter (16-byte aligned; zero-initialised = no step taken yet):
+ *     { int32 t;  int32 rectified;  float c1;  float c2; }
+ * ssa_adam_advance, one thread per record of the list: t += 1, then in double precision, rounded once,
+ *     mode 0 / 1:  c1 = 1 / (1 - beta1^t),  c2 = 1 / sqrt(1 - beta2^t),  rectified = 1
+ *     mode 2:      N_max = 2 / (1 - beta2) - 1,  N_sma = N_max - 2 t beta2^t / (1 - beta2^t),  rectified = N_sma >= 5,
+ *                  c1 = rectified ? sqrt((1 - beta2^t)(N_sma - 4)/(N_max - 4) (N_sma - 2)/N_sma N_max/(N_max - 2)) / (1 - beta1^t)
+ *                                 : 1 / (1 - beta1^t)
+ * ssa_adam_step, elementwise in fp32 with the record of each tensor (call ssa_adam_advance on the same list first):
+ *     mode 0 / 1:  g += weight_decay p;  m += (1 - beta1)(g - m);  v = beta2 v + (1 - beta2) g g;
+ *                  [mode 1: vmax = max(vmax, v)]   p -= lr c1 * m / (sqrt(v | vmax) c2 + eps)
+ *     mode 2:      v = beta2 v + (1 - beta2) g g;  m = beta1 m + (1 - beta1) g;  p += -weight_decay lr p;
+ *                  p -= lr c1 * (rectified ? m / (sqrt(v) + eps) : m)
+ * max_exp_avg_sq is read in mode 1 only (NULL otherwise).  lr_dev and amp_state as in ssa_sgd_momentum_step: the
+ * gradients are multiplied by amp_state[3], and when amp_state[1] != 0 BOTH calls change nothing -- a skipped step
+ * leaves t, m, v, vmax and p as they were.  SSA_EINVAL for a mode outside 0..2, betas outside [0, 1), negative eps
+ * or weight decay, and null or (records) misaligned pointers.                                                       */
+int ssa_adam_advance(void* const* recs, int n_tensors, int mode, double beta1, double beta2,
+                     const float* amp_state, void* stream);
+int ssa_adam_step(void* const* params, const void* const* grads, void* const* exp_avg,
+                  void* const* exp_avg_sq, void* const* max_exp_avg_sq, const void* const* recs,
+                  const int64_t* numel, int n_tensors, int mode, float lr, const float* lr_dev,
+                  double beta1, double beta2, float eps, float weight_decay, const float* amp_state,
+                  void* stream);
+
 /* fp32 elementwise out = a (+ | * | /) b (op 0 | 1 | 2) and its backward (da, db optional): the
  * attention normalisation and the attention-weighted sum over scales of the attention-to-scale
  * heads, network/attnscale.py:153-166,330-352.                                   */

@@ -193,6 +193,9 @@ _SIGS = {
     "ssa_amp_check_grads": ([_P, _P, c_int, _P, _P], c_int),
     "ssa_amp_update": ([_P, c_int, c_float, c_float, c_float, c_float, _P], c_int),
     "ssa_amp_update_counted": ([_P, _P, c_int, c_float, c_float, c_float, c_float, _P], c_int),
+    "ssa_adam_advance": ([_P, c_int, c_int, c_double, c_double, _P, _P], c_int),
+    "ssa_adam_step": ([_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P, c_double, c_double, c_float, c_float,
+                       _P, _P], c_int),
     "ssa_ewise_f32": ([c_int, _P, _P, _P, c_long, _P], c_int),
     "ssa_ewise_bwd_f32": ([c_int, _P, _P, _P, _P, _P, c_long, _P], c_int),
     "ssa_axpy_f32": ([_P, c_float, _P, c_long, c_int, _P], c_int),

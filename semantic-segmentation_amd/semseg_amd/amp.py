@@ -99,12 +99,13 @@ def fp16_storage():
 
 
 def attach_scaler(optimizer, device, **kw):
-    """Give `optimizer` (semseg_amd.loss.optimizer.FusedSGD, possibly behind the graphed proxy) a LossScaler and allow
+    """Give `optimizer` (FusedSGD / FusedAdam / FusedRAdam of semseg_amd.loss.optimizer, possibly behind the graphed proxy) a LossScaler and allow
     the criteria to run backward on the fp16 build.  Returns the scaler."""
     from . import hip_backend
     opt = getattr(optimizer, "_optim", optimizer)
     if not hasattr(opt, "loss_scaler"):
-        raise TypeError("loss scaling needs semseg_amd.loss.optimizer.FusedSGD (got %s)" % type(opt).__name__)
+        raise TypeError("loss scaling needs a fused optimizer of semseg_amd.loss.optimizer: FusedSGD, FusedAdam or "
+                        "FusedRAdam (got %s)" % type(opt).__name__)
     if opt.loss_scaler is None:
         opt.loss_scaler = LossScaler(device, **kw)
         pending = getattr(opt, "_pending_scaler_state", None)

@@ -13,7 +13,7 @@ reference's loop holds so that the UNMODIFIED loop runs the captured step:
     main_loss = net(inputs)      # copy-in + replay: forward, backward AND optimizer step; returns the step's loss
     main_loss.mean().backward()  # a leaf: nothing left to do
     optim.step()                 # no-op (inside the graph); learning-rate changes reach the graph through the
-                                 # optimizer's device scalar (FusedSGD.sync_lr)
+                                 # optimizer's device scalar (sync_lr of the fused optimizers)
 
 Everything the step needs is capture safe by construction (no host synchronisation, torch's caching allocator,
 kernels on the current stream; at N > 1 the SyncBN and gradient exchanges are direct RCCL nodes).
@@ -28,7 +28,7 @@ Guards: at most `max_graphs` input signatures are captured (a run with ragged sh
 activation pools); further signatures, and every step after a capture that raised (logged once), run the SAME
 sequence eagerly.  With N > 1 every rank must see the same shapes in the same iteration (the warm-up steps of a
 capture issue collectives).  Reloading the optimizer's state (`optim.load_state_dict`) drops the captured graphs:
-they hold the addresses of the old momentum buffers.
+they hold the addresses of the old state tensors (momentum buffers, moment estimates, step records).
 """
 import collections
 import os
@@ -36,6 +36,8 @@ import sys
 
 import torch
 from torch import nn
+
+from .loss.optimizer import restore_state, snapshot_state
 
 
 class GraphedTrainStep:
@@ -71,8 +73,10 @@ class GraphedTrainStep:
         # input shape costs the training run nothing but time
         params = [p for g in self.optim.param_groups for p in g["params"]]
         snap_p = [p.detach().clone() for p in params]
-        snap_m = [self.optim.state[p]["momentum_buffer"].clone() if "momentum_buffer" in self.optim.state.get(p, {}) else None
-                  for p in params]
+        # every state tensor of the optimizer (and the fused Adam family's device step records); a foreign optimizer
+        # gets the same treatment through the module-level pair
+        fused = hasattr(self.optim, "snapshot_state")
+        snap_o = self.optim.snapshot_state() if fused else snapshot_state(self.optim)
         bufs = list(self.net.buffers())
         snap_b = [b.detach().clone() for b in bufs]
         scaler = getattr(self.optim, "loss_scaler", None)
@@ -93,14 +97,13 @@ class GraphedTrainStep:
             # also when the capture raised: the warm-up steps must not have trained the network
             torch.cuda.synchronize()
             with torch.no_grad():
-                for p, s0, m0 in zip(params, snap_p, snap_m):
+                for p, s0 in zip(params, snap_p):
                     p.copy_(s0)                     # (bumps the version counter: the captured step re-packs the filters)
-                    buf = self.optim.state.get(p, {}).get("momentum_buffer")
-                    if buf is not None:
-                        if m0 is not None:
-                            buf.copy_(m0)
-                        else:
-                            buf.zero_()             # a zero buffer is the optimizer's first-step state
+                # state that did not exist before goes to zeros (and t = 0): the optimizers' first-step state
+                if fused:
+                    self.optim.restore_state(snap_o)
+                else:
+                    restore_state(self.optim, snap_o)
                 for b, s0 in zip(bufs, snap_b):
                     b.copy_(s0)
                 if snap_s is not None:
@@ -323,7 +326,7 @@ class _GraphedOptim:
         r = self.__dict__["_optim"].load_state_dict(*a, **k)
         st = self.__dict__.get("_stepper")
         if st is not None:
-            st.invalidate()                 # the graphs point at the momentum buffers that were just replaced
+            st.invalidate()                 # the graphs point at the state tensors that were just replaced
         return r
 
     def __getattr__(self, name):
