@@ -13,6 +13,18 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# the emulated share of the exact tests: every strip regime once (ragged, image crossing, tiles_x == 1, interior + border,
+# one strip over the whole problem, the units < nchunk clamp), every epilogue mode, both filter packings
+_EXACT = ("exact_strip and (need_rounding or sliced or grouped or mode0[c48u4-fwd or mode0[c48u64-dgrad or mode0[c48w20-fwd "
+          "or mode0[c96u5-fwd or mode0[c192u16-dgrad or mode0[c384u4-fwd or no_stats[c48w16 or mode1[c48u5-dgrad "
+          "or mode2[c48u4 or mode2[c192u12 or affine[c48u3-res-mode4relu "
+          "or affine[c48w16-res-mode3 or affine[c48u5-nores-mode4relu) or exact_tile_and_tile_aux or exact_wgrad_splitk "
+          "or exact_gemm_wide or exact_dgrad_s2 and (case2 or case4 or case5) "
+          "or exact_igemm and 3-out16 or exact_wgrad_tile and 48-1-37-45-strip2")
+
+_EXACT_F16 = ("exact_strip and (need_rounding or mode0[c48u4-fwd or mode1[c48u5-dgrad or mode2[c48u4 "
+              "or affine[c48u3-res-mode4relu or no_stats[c48w16) or exact_tile_and_tile_aux and case3 or exact_igemm and 3-out16")
+
 # (file, -k expression): each entry a few seconds under emulation
 SELECTION = [
     ("tests/test_kernels_gpu.py", "bce_rmi or scale_fusion or cross_entropy or sigmoid or softmax"),
@@ -22,10 +34,23 @@ SELECTION = [
     # round 5: the fused object attention (19 / 65 / 96 regions, ragged pixel counts, the three-launch form), a grouped
     # weight-gradient launch of more than 16 layers
     ("tests/test_kernels_gpu.py", "ocr_attention or twenty"),
+    # the exact (integer-operand, bit-for-bit) conv tests: the persistent trunk kernel over multi-tile strips in every
+    # epilogue mode, and the small cases of the other conv entry points (the GPU runs the full lists)
+    ("tests/test_kernels_gpu.py", _EXACT),
 ]
+# how many tests an expression must run: a renamed case id would otherwise silently select fewer
+MIN_PASSED = {_EXACT: 46, _EXACT_F16: 10}
 
 
-SELECTION_ENV = []     # (file, -k expression, extra environment)
+# (file, -k expression, extra environment): the fp16-storage build of the same kernels (its own rounding helpers)
+SELECTION_ENV = [("tests/test_kernels_gpu.py", _EXACT_F16, {"SSA_ACT_DTYPE": "fp16"})]
+
+
+def _passed_enough(expr, tail):
+    import re
+    m = re.search(r"(\d+) passed", tail)
+    assert m and int(m.group(1)) >= MIN_PASSED.get(expr, 1), "%r ran %s tests, expected >= %d:\n%s" % (
+        expr, m.group(1) if m else "no", MIN_PASSED.get(expr, 1), tail)
 
 
 def test_selected_kernel_tests_pass_on_the_emulated_kernels():
@@ -37,9 +62,11 @@ def test_selected_kernel_tests_pass_on_the_emulated_kernels():
         tail = "\n".join(r.stdout.splitlines()[-15:])
         assert r.returncode == 0, "%s -k %r under SSA_EMU=1 %r:\n%s\n%s" % (path, expr, extra, tail, r.stderr[-2000:])
         assert " passed" in tail and "failed" not in tail, tail
+        _passed_enough(expr, tail)
     for path, expr in SELECTION:
         r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, path), "-q", "-x", "-m", "gpu", "-k", expr,
                             "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         tail = "\n".join(r.stdout.splitlines()[-15:])
         assert r.returncode == 0, "%s -k %r under SSA_EMU=1:\n%s\n%s" % (path, expr, tail, r.stderr[-2000:])
         assert " passed" in tail and "failed" not in tail, tail
+        _passed_enough(expr, tail)

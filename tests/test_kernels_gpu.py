@@ -1125,3 +1125,609 @@ def test_full_crop_losses(B, C, ign):
     torch.cuda.synchronize()
     check_close("full_ce", out.view(1), loss.view(1), 1e-5, 1e-5)
     check_close("full_ce_grad", nchw(x.grad).cpu(), lr.grad, 1e-4, 1e-4)
+
+
+# ------------------------------------------------------------ exact tests
+# Integer-valued operands: every product is an integer and every partial sum stays below 2^24, so fp32 accumulation is
+# exact in any order, on any tile shape, split or ring depth, and the single round-to-nearest-even to the 16-bit output
+# is what a float64 reference reproduces BIT FOR BIT (tests/exact_util.py; the premise is asserted on the reference).
+# The tolerance of everything below is zero by derivation.  What it pins that check_close cannot see: the rounding mode
+# of the epilogues, the tile walk of the persistent kernel over multi-tile strips, every term of every sum, every pixel
+# of the fused BatchNorm statistics.
+from exact_util import (assert_bits_equal, assert_guard_intact, assert_integers, assert_premise, conv_ref64, guarded, guarded_copy, ints,  # noqa: E402
+                        not_representable, to_act, wgrad_ref64)
+
+# ---- ssa_conv2d_tile_p (csrc/conv_tile_p.hip) with explicit strip units
+# name, Cin, Cout, B, H, W, units
+STRIP_CASES = [
+    ("c48u1", 48, 48, 2, 10, 70, 1),        # one tile per strip (what the suite ran before)
+    ("c48u3", 48, 48, 2, 10, 70, 3),        # 3 tiles per strip = one tile row: every strip ends in a row wrap
+    ("c48u4", 48, 48, 2, 10, 70, 4),        # 4, 4, 4, 4, 2: ragged last strip, strip 2 runs from image 0 into image 1
+    ("c48u5", 48, 40, 2, 10, 70, 5),        # 5, 5, 5, 3; Cout = 40: the second n-block is 8 channels wide
+    ("c48u64", 48, 48, 2, 10, 70, 64),      # one strip covers the whole problem (18 tiles)
+    ("c48w20", 48, 48, 2, 11, 20, 2),       # tiles_x == 1: every advance wraps; 3 tiles per image, strips of 2
+    ("c48w16", 48, 24, 1, 5, 16, 64),       # the narrowest supported image, H = 5: one pixel row in the second tile row
+    ("c96u6", 96, 96, 2, 9, 33, 6),         # two chunks per tile, 3 tiles per strip, W = 33: a one-pixel tile column
+    ("c96u10", 96, 72, 1, 14, 100, 10),     # interior tiles (the fast path of fetch) and border tiles in one strip
+    ("c96u5", 96, 40, 1, 14, 100, 5),       # strips of 2 over the same image: (border, interior), (interior, border)
+    ("c192u12", 192, 64, 1, 6, 40, 12),     # four chunks per tile, 2 tiles per strip (nstrips rebalances 3 -> 2)
+    ("c192u16", 192, 40, 2, 9, 33, 16),     # four chunks, 6 tiles per image, strips of 4: the middle strip crosses the images
+    ("c384u4", 384, 40, 1, 5, 33, 4),       # units < nchunk = 8: the tpw < 1 clamp
+    ("c384u24", 384, 32, 1, 9, 33, 24),     # eight chunks per tile, 3 tiles per strip
+]
+_STRIP_IDS = [c[0] for c in STRIP_CASES]
+
+
+def _strip_plan(case):
+    """Mirror of launch_p (csrc/conv_tile_p.hip): the strips of this case as lists of (image, tile row, tile column)."""
+    _, Cin, Cout, B, H, W, units = case
+    tiles_x, tiles_y = -(-W // 32), -(-H // 4)
+    total = B * tiles_x * tiles_y
+    nchunk = Cin // 48
+    tpw = max(1, min(units, 64) // nchunk)
+    nstrips = -(-total // tpw)
+    tiles_per_wg = -(-total // nstrips)
+    tiles = [(b, ty, tx) for b in range(B) for ty in range(tiles_y) for tx in range(tiles_x)]
+    strips = [tiles[i:i + tiles_per_wg] for i in range(0, total, tiles_per_wg)]
+
+    def interior(t):
+        x0, y0 = t[2] * 32, t[1] * 4
+        return x0 >= 1 and y0 >= 1 and x0 + 33 <= W and y0 + 5 <= H
+    return dict(tiles_x=tiles_x, tiles_y=tiles_y, total=total, nchunk=nchunk, units=units, tiles_per_wg=tiles_per_wg,
+                per_image=tiles_x * tiles_y, strips=strips, ragged=len(strips[-1]) < tiles_per_wg,
+                crosses=any(len({t[0] for t in s}) > 1 for s in strips),
+                mixed=any(any(interior(t) for t in s) and not all(interior(t) for t in s) for s in strips))
+
+
+def _assert_strip_coverage(cases):
+    """A condition on the parameter list, not a measurement: a later edit of the list cannot silently drop a regime."""
+    plans = [(c, _strip_plan(c)) for c in cases]
+    tpws = {p["tiles_per_wg"] for _, p in plans}
+    assert {1, 2, 3} <= tpws and max(tpws) >= 5, tpws
+    assert any(p["ragged"] for _, p in plans), "no ragged last strip"
+    assert any(c[3] == 2 and p["per_image"] % p["tiles_per_wg"] and p["crosses"] for c, p in plans), "no strip crosses an image boundary"
+    assert any(c[3] == 2 and p["nchunk"] > 1 and p["per_image"] % p["tiles_per_wg"] and p["crosses"] for c, p in plans), \
+        "no multi-chunk strip crosses an image boundary"
+    assert any(p["tiles_x"] == 1 and 16 <= c[5] <= 32 and p["tiles_per_wg"] > 1 for c, p in plans), "no tiles_x == 1 case"
+    assert any(c[5] % 32 and c[4] % 4 for c, _ in plans), "no case with W % 32 != 0 and H % 4 != 0"
+    assert any(c[5] >= 97 and c[4] >= 13 and p["mixed"] for c, p in plans), "no strip mixes interior and border tiles"
+    assert any(c[6] == 64 and len(p["strips"]) == 1 and p["total"] > 1 for c, p in plans), "no single strip over a whole problem"
+    assert any(c[1] == 384 and c[6] < p["nchunk"] and p["tiles_per_wg"] == 1 for c, p in plans), "no units < nchunk case"
+    assert {c[1] for c in cases} == {48, 96, 192, 384}
+    for c, p in plans:
+        assert c[5] >= 16 and c[2] % 8 == 0 and sum(len(s) for s in p["strips"]) == p["total"], c
+
+
+_assert_strip_coverage(STRIP_CASES)
+
+# Operand amplitudes (x and w uniform integers in [-a, a]) per input-channel count.
+#   narrow: for the cases with statistics.  The kernel sums y and y^2 of the rounded outputs in fp32 over a strip, so the
+#     premise there is sum_pixels y^2 < 2^24 per channel (asserted on the reference, over the WHOLE problem: an upper
+#     bound of any strip); outputs reach a few hundred -- above 2^8, so the bf16 rounding, ties included, decides bits.
+#   wide: for the epilogues without statistics (aux modes 1, 3, 4 and mode 0 without stats).  Outputs reach several
+#     thousand -- above 2^11, so the fp16 build rounds too -- and stay far below the fp16 maximum after a scale of 4.
+_AMP_NARROW = {48: (4, 2), 96: (3, 2), 192: (2, 2), 384: (2, 1)}
+_AMP_WIDE = {48: (15, 15), 96: (12, 12), 192: (10, 10), 384: (8, 8)}
+
+
+def _strip_operands(case, wide, seed=0):
+    _, Cin, Cout, B, H, W, _ = case
+    ax, aw = (_AMP_WIDE if wide else _AMP_NARROW)[Cin]
+    return ints((B, Cin, H, W), -ax, ax, seed + 100), ints((Cout, Cin, 3, 3), -aw, aw, seed + 101)
+
+
+def _ref_nhwc(case, x, w):
+    """float64 conv [B,H,W,Cout] and how many of its values the 16-bit format cannot hold"""
+    ref = conv_ref64(x, w, None, 1, 1, 1).permute(0, 2, 3, 1).contiguous()
+    n = not_representable(ref)
+    print("[exact %s] max |y| = %d, %d of %d outputs are not representable in %s" % (
+        case[0], int(ref.abs().max()), n, ref.numel(), ACT_DTYPE))
+    return ref, n
+
+
+def _pack_for_tile(hb, w, tr):
+    """Fragment-order filter of the conv with OIHW weight w: forward packing (ssa_pack_filter mode 2), or the
+    data-gradient packing (mode 3) of the forward weight whose data gradient this conv is.  Returns (packed, keep-alive)."""
+    if tr:
+        wt = w.flip(2, 3).permute(1, 0, 2, 3).contiguous().to(DEV)       # [Cin_fwd = Cout here][Cout_fwd = Cin here], taps flipped
+        return hb._packed_filter(wt, 3, 0, w.shape[1])[0], wt
+    wd = w.to(DEV)
+    return hb._packed_filter(wd, 2, w.shape[1], 0)[0], wd
+
+
+def _launch_tile_p(case, x, w, mode=0, tr=False, stats=False, aux=None, ldaux=None, coef=None, ldx=None, ldy=None,
+                   strip=True, packed=None):
+    """One ssa_conv2d_tile_p launch through the C ABI inside ssa_conv_tile_strip(units) ... (0).  Input, output and
+    statistics live in guarded buffers (NaN all around, the output pre-filled with NaN)."""
+    import ctypes
+    from semseg_amd._lib import check
+    hb = _hb()
+    L = hb.lib()
+    _, Cin, Cout, B, H, W, units = case
+    xg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV, ldx)
+    wp, keep = packed if packed is not None else _pack_for_tile(hb, w, tr)
+    d = hb._tile_desc(B, H, W, Cin, ldx or Cin, Cout, (3, 3), 1, 1, 1, H, W, False)
+    d.ldy = ldy or Cout
+    assert L.ssa_conv2d_tile_p_supported(ctypes.byref(d)) == 1
+    yg = guarded((B, H, W, Cout), ACT_DTYPE, DEV, ldy)
+    sg = None
+    if stats:
+        sg = guarded((hb.stat_replicas(), 2, Cout), torch.float64, DEV)
+        sg.view.zero_()
+    ag = guarded_copy(aux.to(ACT_DTYPE), DEV, ldaux) if aux is not None else None
+    cd = coef.to(DEV).contiguous() if coef is not None else None
+    gs = [g for g in (xg, yg, sg, ag) if g is not None]
+
+    def go():
+        check(L.ssa_conv2d_tile_p(ctypes.byref(d), hb._p(xg.view), hb._p(wp), None, hb._p(yg.view),
+                                  hb._p(sg.view) if sg else None, hb._p(ag.view) if ag else None,
+                                  (ldaux or Cout) if ag else 0, hb._p(cd), mode, hb._s()), "ssa_conv2d_tile_p")
+    if not strip:           # the caller brackets (a grouped level)
+        go()
+        return yg, sg, gs + [keep, cd, wp]
+    L.ssa_conv_tile_strip(units)
+    try:
+        go()
+    finally:
+        L.ssa_conv_tile_strip(0)
+    if xg.view.is_cuda:
+        torch.cuda.synchronize()
+    assert_guard_intact("tile_p %s" % case[0], *gs)
+    return yg, sg
+
+
+def _check_stats(name, sg, want0, want1):
+    """Both rows of the summed replicas against float64 sums, with torch.equal: no pixel missing, none counted twice."""
+    got = sg.view.sum(0).cpu()
+    for row, want, what in ((0, want0, "sums"), (1, want1, "second sums")):
+        if not torch.equal(got[row], want):
+            c = int((got[row] != want).nonzero()[0])
+            raise AssertionError("%s %s differ in %d channels; first: channel %d got %r want %r" % (
+                name, what, int((got[row] != want).sum()), c, float(got[row][c]), float(want[c])))
+
+
+def test_exact_strip_cases_need_rounding():
+    """The operands of the strip tests exercise the rounding: for every Cin at least one case has outputs the 16-bit
+    format cannot hold (wide operands: both builds; narrow operands, the cases with statistics: bf16, whose mantissa
+    ends at 2^8 -- fp16 holds every integer up to 2^11 and sum y^2 < 2^24 leaves no room above that)."""
+    for Cin in (48, 96, 192, 384):
+        cases = [c for c in STRIP_CASES if c[1] == Cin]
+        assert sum(_ref_nhwc(c, *_strip_operands(c, True))[1] for c in cases) > 0, Cin
+        if ACT_DTYPE == torch.bfloat16:
+            assert sum(_ref_nhwc(c, *_strip_operands(c, False))[1] for c in cases) > 0, Cin
+
+
+@pytest.mark.parametrize("tr", [False, True], ids=["fwd", "dgrad"])
+@pytest.mark.parametrize("case", STRIP_CASES, ids=_STRIP_IDS)
+def test_exact_strip_mode0(case, tr):
+    """aux_mode 0: the output bit for bit, every element written (the buffer starts as NaN), and the BatchNorm sums of
+    the ROUNDED outputs equal to the float64 sums -- one missing or doubled pixel, one wrong channel of one tile fails."""
+    hb = _hb()
+    hb.clear_pack_cache()
+    p = _strip_plan(case)
+    x, w = _strip_operands(case, False)
+    ref, _ = _ref_nhwc(case, x, w)
+    want = to_act(ref)
+    r = want.double().view(-1, case[2])
+    assert_premise("sum of y^2 over the pixels", (r * r).sum(0))       # the kernel's fp32 strip sums are then exact
+    yg, sg = _launch_tile_p(case, x, w, 0, tr, stats=True)
+    assert_bits_equal("tile_p mode 0 %s" % case[0], yg.view.cpu(), want, tile=(4, 32, p["tiles_per_wg"]))
+    _check_stats("tile_p mode 0 %s" % case[0], sg, r.sum(0), (r * r).sum(0))
+    hb.clear_pack_cache()
+
+
+@pytest.mark.parametrize("case", STRIP_CASES, ids=_STRIP_IDS)
+def test_exact_strip_mode0_wide_no_stats(case):
+    """aux_mode 0 without statistics on the wide operands: outputs of several thousand, rounded in both builds."""
+    hb = _hb()
+    hb.clear_pack_cache()
+    x, w = _strip_operands(case, True)
+    ref, _ = _ref_nhwc(case, x, w)
+    yg, _ = _launch_tile_p(case, x, w, 0, False)
+    assert_bits_equal("tile_p wide %s" % case[0], yg.view.cpu(), to_act(ref), tile=(4, 32, _strip_plan(case)["tiles_per_wg"]))
+    hb.clear_pack_cache()
+
+
+@pytest.mark.parametrize("tr", [False, True], ids=["fwd", "dgrad"])
+@pytest.mark.parametrize("case", STRIP_CASES, ids=_STRIP_IDS)
+def test_exact_strip_mode1(case, tr):
+    """aux_mode 1: y = r16(r16(conv) + aux), two roundings by specification (include/semseg_hip.h, ssa_conv2d_tile_aux;
+    csrc/conv_tile_p.hip `f[j] += xv[j]; o = pack8(f)` on the unpacked 16-bit conv output).  Both are reproduced: the
+    intermediate is a 16-bit value, the integer aux tile (pixel stride ldaux > Cout, NaN neighbours) is added exactly."""
+    hb = _hb()
+    hb.clear_pack_cache()
+    _, Cin, Cout, B, H, W, _ = case
+    x, w = _strip_operands(case, True)
+    ref, _ = _ref_nhwc(case, x, w)
+    aux = ints((B, H, W, Cout), -100, 100, 7)
+    want = to_act(to_act(ref).double() + aux.double())
+    yg, _ = _launch_tile_p(case, x, w, 1, tr, aux=aux, ldaux=Cout + 24)
+    assert_bits_equal("tile_p mode 1 %s" % case[0], yg.view.cpu(), want, tile=(4, 32, _strip_plan(case)["tiles_per_wg"]))
+    hb.clear_pack_cache()
+
+
+def _bn_coef(Cout, seed):
+    """[4][Cout] coefficient table that keeps the epilogue exact: scale = +-2^k (mixed gamma signs), integer shift,
+    integer mean, invstd a power of two."""
+    g = torch.Generator().manual_seed(seed)
+    scale = 2.0 ** torch.randint(-2, 3, (Cout,), generator=g).float() * (torch.randint(0, 2, (Cout,), generator=g).float() * 2 - 1)
+    assert (scale > 0).any() and (scale < 0).any()
+    shift = torch.randint(-2, 3, (Cout,), generator=g).float()
+    mean = torch.randint(-2, 3, (Cout,), generator=g).float()
+    invstd = 2.0 ** torch.randint(-2, 2, (Cout,), generator=g).float()
+    return torch.stack([scale, shift, mean, invstd])
+
+
+@pytest.mark.parametrize("case", STRIP_CASES, ids=_STRIP_IDS)
+def test_exact_strip_mode2(case):
+    """aux_mode 2 (the data-gradient packing, as the product uses it): y = dz untouched, and the BatchNorm backward sums
+    sum(m dz), sum(m dz xhat) with m = [scale x + shift > 0] exactly -- gamma signs mixed, many pre-activations exactly
+    0 (the comparison is strict), the integer x tile at ldaux > Cout."""
+    hb = _hb()
+    hb.clear_pack_cache()
+    _, Cin, Cout, B, H, W, _ = case
+    x, w = _strip_operands(case, False)
+    ref, _ = _ref_nhwc(case, x, w)
+    dz = to_act(ref)
+    a = ints((B, H, W, Cout), -3, 3, 8)
+    coef = _bn_coef(Cout, 9)
+    c = coef.double()
+    pre = a.double() * c[0] + c[1]
+    assert int((pre == 0).sum()) > a.numel() // 50, "too few pre-activations are exactly zero"
+    m = (pre > 0).double()
+    dzd = dz.double()
+    assert_premise("sum |dz| |x|", (dzd.abs() * a.double().abs()).view(-1, Cout).sum(0))
+    want0 = (m * dzd).view(-1, Cout).sum(0)
+    want1 = (m * dzd * (a.double() - c[2]) * c[3]).view(-1, Cout).sum(0)
+    yg, sg = _launch_tile_p(case, x, w, 2, True, stats=True, aux=a, ldaux=Cout + 8, coef=coef)
+    assert_bits_equal("tile_p mode 2 %s" % case[0], yg.view.cpu(), dz, tile=(4, 32, _strip_plan(case)["tiles_per_wg"]))
+    _check_stats("tile_p mode 2 %s" % case[0], sg, want0, want1)
+    hb.clear_pack_cache()
+
+
+@pytest.mark.parametrize("relu", [False, True], ids=["mode3", "mode4relu"])
+@pytest.mark.parametrize("res", [False, True], ids=["nores", "res"])
+@pytest.mark.parametrize("case", STRIP_CASES, ids=_STRIP_IDS)
+def test_exact_strip_affine(case, res, relu):
+    """aux_mode 3 / 4 (inference): z = r16(act(scale * r16(conv) + shift [+ residual])) -- the conv output is rounded to 16
+    bits FIRST, as the header specifies; scales +-2^k and integer shifts keep the affine step exact."""
+    hb = _hb()
+    hb.clear_pack_cache()
+    _, Cin, Cout, B, H, W, _ = case
+    x, w = _strip_operands(case, True)
+    ref, _ = _ref_nhwc(case, x, w)
+    coef = _bn_coef(Cout, 10)
+    coef[1] = ints((Cout,), -50, 50, 11)
+    coef[2:] = 0
+    c = coef.double()
+    z = to_act(ref).double() * c[0] + c[1]
+    r = ints((B, H, W, Cout), -100, 100, 12) if res else None
+    if res:
+        z = z + r.double()
+    if relu:
+        z = torch.relu(z)
+    assert float(z.abs().max()) < 60000.0            # finite in fp16
+    yg, _ = _launch_tile_p(case, x, w, 4 if relu else 3, False, aux=r, ldaux=Cout + 16 if res else None, coef=coef)
+    assert_bits_equal("tile_p affine %s" % case[0], yg.view.cpu(), to_act(z), tile=(4, 32, _strip_plan(case)["tiles_per_wg"]))
+    hb.clear_pack_cache()
+
+
+@pytest.mark.parametrize("which", ["ldy", "ldx"])
+def test_exact_strip_sliced_buffers(which):
+    """ldy > Cout: the output is a channel slice whose neighbouring channels must keep their NaN pattern; ldx > Cin: the
+    input is a channel slice whose neighbours ARE NaN -- one stray channel read poisons the output."""
+    hb = _hb()
+    hb.clear_pack_cache()
+    case = dict(zip(_STRIP_IDS, STRIP_CASES))["c48u5" if which == "ldy" else "c96u6"]
+    x, w = _strip_operands(case, False)
+    ref, _ = _ref_nhwc(case, x, w)
+    want = to_act(ref)
+    r = want.double().view(-1, case[2])
+    kw = dict(ldy=case[2] + 24) if which == "ldy" else dict(ldx=case[1] + 32)
+    yg, sg = _launch_tile_p(case, x, w, 0, False, stats=True, **kw)
+    assert_bits_equal("tile_p %s %s" % (which, case[0]), yg.view.cpu(), want, tile=(4, 32, _strip_plan(case)["tiles_per_wg"]))
+    _check_stats("tile_p %s" % which, sg, r.sum(0), (r * r).sum(0))
+    hb.clear_pack_cache()
+
+
+def test_exact_strip_grouped_level():
+    """Problems of different Cin as ONE grouped level under one explicit strip length > 1 (what BasicBlockGroupFn does
+    through hb.tile_strip): each equals its exact reference and its own single launch bit for bit, statistics included."""
+    hb = _hb()
+    L = hb.lib()
+    hb.clear_pack_cache()
+    units = 8
+    level = [("g48", 48, 48, 2, 9, 40, units), ("g96", 96, 40, 1, 6, 33, units), ("g192", 192, 32, 1, 5, 20, units),
+             ("g48b", 48, 24, 1, 14, 100, units)]
+    assert all(_strip_plan(c)["tiles_per_wg"] > 1 for c in level)
+    ops = [_strip_operands(c, False, seed=10 * i) for i, c in enumerate(level)]
+    single = [_launch_tile_p(c, x, w, 0, False, stats=True) for c, (x, w) in zip(level, ops)]
+    packs = [_pack_for_tile(hb, w, False) for _, w in ops]          # (the packing launches stay outside the count)
+    L.ssa_launch_count(1)
+    L.ssa_conv_tile_strip(units)
+    try:
+        with hb.group():
+            grouped = [_launch_tile_p(c, x, w, 0, False, stats=True, strip=False, packed=pk)
+                       for c, (x, w), pk in zip(level, ops, packs)]
+    finally:
+        L.ssa_conv_tile_strip(0)
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    assert L.ssa_launch_count(1) == 1
+    for c, (x, w), (y1, s1), (y2, s2, gs) in zip(level, ops, single, grouped):
+        assert_guard_intact("grouped %s" % c[0], *[g for g in gs if hasattr(g, "inside")])
+        want = to_act(_ref_nhwc(c, x, w)[0])
+        tile = (4, 32, _strip_plan(c)["tiles_per_wg"])
+        assert_bits_equal("grouped %s vs reference" % c[0], y2.view.cpu(), want, tile=tile)
+        assert_bits_equal("grouped %s vs single launch" % c[0], y2.view.cpu(), y1.view.cpu(), tile=tile)
+        r = want.double().view(-1, c[2])
+        _check_stats("grouped %s" % c[0], s2, r.sum(0), (r * r).sum(0))
+        assert torch.equal(s2.view.sum(0).cpu(), s1.view.sum(0).cpu())
+    hb.clear_pack_cache()
+
+
+# ---- the same exact check on the other convolution entry points (the case lists of the statistical tests above)
+def _exact_fwd_check(name, y, st, ref, Cout):
+    """Output bits, every element written; the BatchNorm sums of the rounded outputs with torch.equal."""
+    want = to_act(ref)
+    assert_bits_equal(name, y.view.cpu(), want)
+    if st is not None:
+        r = want.double().view(-1, Cout)
+        assert_premise(name + ": sum of y^2 over the pixels", (r * r).sum(0))
+        _check_stats(name, st, r.sum(0), (r * r).sum(0))
+    assert_guard_intact(name, *[g for g in (y, st) if g is not None])
+
+
+def _stats_buf(hb, Cout, on):
+    if not on:
+        return None
+    sg = guarded((hb.stat_replicas(), 2, Cout), torch.float64, DEV)
+    sg.view.zero_()
+    return sg
+
+
+@pytest.mark.parametrize("case", HALO_REG_CASES)
+def test_exact_halo_reg_3x3(case):
+    """ssa_conv2d_halo_reg on the cases of test_halo_reg_3x3, integer operands: bits of the output, sums of the stats."""
+    import ctypes
+    from semseg_amd._lib import check
+    hb = _hb()
+    B, H, W, Cin, Cout, bias, stats, tr = case
+    x, w = ints((B, Cin, H, W), -2, 2, 3), ints((Cout, Cin, 3, 3), -2, 2, 4)
+    b = ints((Cout,), -5, 5, 5) if bias else None
+    ref = conv_ref64(x, w, b, 1, 1, 1).permute(0, 2, 3, 1).contiguous()
+    print("[exact halo_reg] %d outputs not representable" % not_representable(ref))
+    hb.clear_pack_cache()
+    xg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV)
+    wp, keep = _pack_for_tile(hb, w, tr)
+    d = hb._tile_desc(B, H, W, Cin, Cin, Cout, (3, 3), 1, 1, 1, H, W, False)
+    L = hb.lib()
+    assert L.ssa_conv2d_halo_reg_supported(ctypes.byref(d)) == 1
+    yg, sg = guarded((B, H, W, Cout), ACT_DTYPE, DEV), _stats_buf(hb, Cout, stats)
+    bd = b.to(DEV) if b is not None else None
+    check(L.ssa_conv2d_halo_reg(ctypes.byref(d), hb._p(xg.view), hb._p(wp), hb._p(bd), hb._p(yg.view),
+                                hb._p(sg.view) if sg else None, hb._s()), "halo_reg")
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    _exact_fwd_check("halo_reg %s" % (case,), yg, sg, ref, Cout)
+    hb.clear_pack_cache()
+
+
+@pytest.mark.parametrize("case", WIDE_CASES)
+def test_exact_gemm_wide_1x1(case):
+    """ssa_conv2d_gemm_wide on the cases of test_gemm_wide_1x1, integer operands."""
+    import ctypes
+    from semseg_amd._lib import check
+    hb = _hb()
+    B, H, W, Cin, Cout, bias, stats, tr = case
+    x, w = ints((B, Cin, H, W), -4, 4, 3), ints((Cout, Cin, 1, 1), -4, 4, 4)
+    b = ints((Cout,), -5, 5, 5) if bias else None
+    ref = conv_ref64(x, w, b, 1, 0, 1).permute(0, 2, 3, 1).contiguous()
+    print("[exact gemm_wide] %d outputs not representable" % not_representable(ref))
+    hb.clear_pack_cache()
+    xg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV)
+    if tr:
+        keep = w[:, :, 0, 0].t().contiguous().view(Cin, Cout, 1, 1).to(DEV)
+        wp, _ = hb._packed_filter(keep, 3, 0, Cin)
+    else:
+        keep = w.to(DEV)
+        wp, _ = hb._packed_filter(keep, 2, Cin, 0)
+    d = hb._tile_desc(B, H, W, Cin, Cin, Cout, (1, 1), 1, 0, 1, H, W, False)
+    L = hb.lib()
+    yg, sg = guarded((B, H, W, Cout), ACT_DTYPE, DEV), _stats_buf(hb, Cout, stats)
+    bd = b.to(DEV) if b is not None else None
+    check(L.ssa_conv2d_gemm_wide(ctypes.byref(d), hb._p(xg.view), hb._p(wp), hb._p(bd), hb._p(yg.view),
+                                 hb._p(sg.view) if sg else None, hb._s()), "wide")
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    _exact_fwd_check("gemm_wide %s" % (case,), yg, sg, ref, Cout)
+    hb.clear_pack_cache()
+
+
+@pytest.mark.parametrize("out_f32", [False, True], ids=["out16", "out32"])
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5])
+def test_exact_igemm_tile_configs(cfg, out_f32):
+    """ssa_conv2d_igemm(_stats): all six tile configurations on the ragged shape of test_conv_all_tile_configs, with
+    bias; 16-bit output (+ statistics) and fp32 output (an exact integer: no rounding at all)."""
+    hb = _hb()
+    B, H, W, Cin, Cout = 1, 37, 45, 72, 88
+    x, w, b = ints((B, Cin, H, W), -3, 3, 3), ints((Cout, Cin, 3, 3), -2, 2, 4), ints((Cout,), -5, 5, 5)
+    ref = conv_ref64(x, w, b, 1, 1, 1).permute(0, 2, 3, 1).contiguous()
+    hb.clear_pack_cache()
+    xg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV)
+    wd = w.to(DEV)
+    wp, Kpad = hb._packed_filter(wd, 0, Cin, 0)
+    yg = guarded((B, H, W, Cout), torch.float32 if out_f32 else ACT_DTYPE, DEV)
+    sg = _stats_buf(hb, Cout, not out_f32)
+    hb._igemm(xg.view, Cin, (B, H, W, Cin), wp, Kpad, b.to(DEV), (H, W), Cout, (3, 3), 1, 1, 1, False, out_f32, cfg=cfg,
+              stats=sg.view if sg else None, out=yg.view)
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    if out_f32:
+        assert_bits_equal("igemm cfg%d fp32" % cfg, yg.view.cpu(), ref.float())
+        assert_guard_intact("igemm cfg%d fp32" % cfg, yg)
+    else:
+        print("[exact igemm] %d outputs not representable" % not_representable(ref))
+        _exact_fwd_check("igemm cfg%d" % cfg, yg, sg, ref, Cout)
+    hb.clear_pack_cache()
+
+
+# B, H, W, Cin, Cout: shapes ssa_conv2d_tile_p does not take (64 channels; W < 16)
+TILE_EXACT_CASES = [(1, 9, 20, 64, 64), (2, 20, 12, 48, 96), (1, 9, 7, 96, 48), (1, 33, 18, 64, 24)]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("case", TILE_EXACT_CASES)
+def test_exact_tile_and_tile_aux(case, mode):
+    """ssa_conv2d_tile (mode 0: bias + statistics) and ssa_conv2d_tile_aux (1: r16(r16(conv) + aux), two roundings by
+    specification; 2: the BatchNorm backward sums) of csrc/conv_tile.hip on 64-channel and W < 16 shapes."""
+    import ctypes
+    from semseg_amd._lib import check
+    hb = _hb()
+    L = hb.lib()
+    B, H, W, Cin, Cout = case
+    x, w = ints((B, Cin, H, W), -3, 3, 21), ints((Cout, Cin, 3, 3), -2, 2, 22)
+    b = ints((Cout,), -5, 5, 23) if mode == 0 else None
+    ref = conv_ref64(x, w, b, 1, 1, 1).permute(0, 2, 3, 1).contiguous()
+    hb.clear_pack_cache()
+    xg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV)
+    wp, keep = _pack_for_tile(hb, w, mode != 0)
+    d = hb._tile_desc(B, H, W, Cin, Cin, Cout, (3, 3), 1, 1, 1, H, W, False)
+    assert L.ssa_conv2d_tile_supported(ctypes.byref(d)) == 1 and L.ssa_conv2d_tile_p_supported(ctypes.byref(d)) == 0
+    yg, sg = guarded((B, H, W, Cout), ACT_DTYPE, DEV), _stats_buf(hb, Cout, mode != 1)
+    name = "tile mode %d %s" % (mode, case)
+    if mode == 0:
+        check(L.ssa_conv2d_tile(ctypes.byref(d), hb._p(xg.view), hb._p(wp), hb._p(b.to(DEV)), hb._p(yg.view), hb._p(sg.view),
+                                hb._s()), "ssa_conv2d_tile")
+        if DEV != "cpu":
+            torch.cuda.synchronize()
+        _exact_fwd_check(name, yg, sg, ref, Cout)
+    else:
+        a = ints((B, H, W, Cout), -100, 100, 24) if mode == 1 else ints((B, H, W, Cout), -3, 3, 24)
+        ag = guarded_copy(a.to(ACT_DTYPE), DEV, Cout + 8)
+        coef = _bn_coef(Cout, 25)
+        cd = coef.to(DEV)
+        check(L.ssa_conv2d_tile_aux(ctypes.byref(d), hb._p(xg.view), hb._p(wp), None, hb._p(yg.view),
+                                    hb._p(sg.view) if sg else None, hb._p(ag.view), Cout + 8, hb._p(cd) if mode == 2 else None,
+                                    mode, hb._s()), "ssa_conv2d_tile_aux")
+        if DEV != "cpu":
+            torch.cuda.synchronize()
+        dz = to_act(ref)
+        if mode == 1:
+            assert_bits_equal(name, yg.view.cpu(), to_act(dz.double() + a.double()))
+        else:
+            c = coef.double()
+            m = (a.double() * c[0] + c[1] > 0).double()
+            dzd = dz.double()
+            assert_premise("sum |dz| |x|", (dzd.abs() * a.double().abs()).view(-1, Cout).sum(0))
+            assert_bits_equal(name, yg.view.cpu(), dz)
+            _check_stats(name, sg, (m * dzd).view(-1, Cout).sum(0), (m * dzd * (a.double() - c[2]) * c[3]).view(-1, Cout).sum(0))
+        assert_guard_intact(name, *[g for g in (xg, yg, sg, ag) if g is not None])
+    hb.clear_pack_cache()
+
+
+# B, H, W, Cin, Cout of the forward stride-2 conv: even / odd extents, Cout no multiple of 32, one-pixel classes
+DGRAD_S2_EXACT_CASES = [(2, 31, 50, 96, 96), (1, 17, 16, 192, 384), (1, 37, 45, 48, 96), (2, 33, 64, 96, 200),
+                        (1, 2, 3, 48, 24), (1, 1, 9, 48, 48), (1, 64, 64, 48, 96)]
+
+
+@pytest.mark.parametrize("case", DGRAD_S2_EXACT_CASES)
+def test_exact_dgrad_s2(case):
+    """ssa_conv2d_dgrad_s2 (four parity classes) against the exact transposed reference: the float64 gradient of the
+    stride-2 conv with respect to its input."""
+    import ctypes
+    from semseg_amd._lib import check
+    hb = _hb()
+    B, H, W, Cin, Cout = case
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    w, dy = ints((Cout, Cin, 3, 3), -2, 2, 31), ints((B, Cout, Ho, Wo), -3, 3, 32)
+    assert_integers("dgrad_s2", w, dy)
+    F = torch.nn.functional
+
+    def dgrad(ww, gg):
+        xx = torch.zeros(B, Cin, H, W, dtype=torch.float64, requires_grad=True)
+        F.conv2d(xx, ww, None, 2, 1, 1).backward(gg)
+        return xx.grad.permute(0, 2, 3, 1).contiguous()
+    assert_premise("dgrad_s2", dgrad(w.double().abs(), dy.double().abs()))
+    ref = dgrad(w.double(), dy.double())
+    print("[exact dgrad_s2] %d outputs not representable" % not_representable(ref))
+    hb.clear_pack_cache()
+    wd = w.to(DEV)
+    dg = guarded_copy(nhwc(dy).to(ACT_DTYPE), DEV)
+    packs = [hb._packed_filter(wd, 4 + c, 0, Cout) for c in range(4)]
+    dxg = guarded((B, H, W, Cin), ACT_DTYPE, DEV)
+    wp = (ctypes.c_void_p * 4)(*[t.data_ptr() for t, _ in packs])
+    kp = (ctypes.c_int * 4)(*[k for _, k in packs])
+    check(hb.lib().ssa_conv2d_dgrad_s2(B, H, W, Cin, Cin, Ho, Wo, Cout, Cout, hb._p(dg.view), wp, kp, hb._p(dxg.view),
+                                       hb._s()), "ssa_conv2d_dgrad_s2")
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    assert_bits_equal("dgrad_s2 %s" % (case,), dxg.view.cpu(), to_act(ref))
+    assert_guard_intact("dgrad_s2 %s" % (case,), dg, dxg)
+    hb.clear_pack_cache()
+
+
+def _exact_wgrad(kind, B, H, W, Cin, Cout, k, stride, pad, cfg, amp=3):
+    """One weight-gradient kernel (`kind`: tile / head / wgrad = split-K) + ssa_conv2d_wgrad_reduce through the C ABI:
+    the fp32 gradient bit for bit (an exact integer: sum |x| |dy| over all pixels < 2^24, asserted on the reference).
+    The fp32 partial buffer starts as NaN: a block no workgroup writes poisons the reduce."""
+    import ctypes
+    from semseg_amd._lib import check, ConvDesc
+    hb = _hb()
+    L = hb.lib()
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    x, dy = ints((B, Cin, H, W), -amp, amp, 41), ints((B, Cout, Ho, Wo), -amp, amp, 42)
+    ref = wgrad_ref64(x, dy, k, stride, pad, 1)
+    xg, gg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV), guarded_copy(nhwc(dy).to(ACT_DTYPE), DEV)
+    d = ConvDesc(B, H, W, Cin, Cin, Ho, Wo, Cout, Cout, k, k, stride, pad, 1, 0, 0, 0, cfg)
+    ns, ws = ctypes.c_int(0), ctypes.c_size_t(0)
+    plan = {"tile": L.ssa_conv2d_wgrad_tile_plan, "head": L.ssa_conv2d_wgrad_head_plan, "wgrad": L.ssa_conv2d_wgrad_plan}[kind]
+    fn = {"tile": L.ssa_conv2d_wgrad_tile, "head": L.ssa_conv2d_wgrad_head, "wgrad": L.ssa_conv2d_wgrad}[kind]
+    check(plan(ctypes.byref(d), Cout, ctypes.byref(ns), ctypes.byref(ws)), "plan")
+    part = guarded((ws.value // 4,), torch.float32, DEV)
+    dw = guarded((Cout, Cin, k, k), torch.float32, DEV)
+    check(fn(ctypes.byref(d), hb._p(xg.view), hb._p(gg.view), Cout, Cout, ns.value, hb._p(part.view), hb._s()), kind)
+    check(L.ssa_conv2d_wgrad_reduce(hb._p(part.view), ns.value, Cout, Cout, Cin, Cin, k, k, hb._p(dw.view), 0, hb._s()),
+          "ssa_conv2d_wgrad_reduce")
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    name = "%s wgrad %s cfg %d (%d splits)" % (kind, (B, H, W, Cin, Cout, k, stride), cfg, ns.value)
+    assert_bits_equal(name, dw.view.cpu(), ref.float())
+    assert_guard_intact(name, xg, gg, part, dw)
+    return ns.value
+
+
+@pytest.mark.parametrize("cfg", [-1, 1, 2, 3], ids=["default", "strip1", "strip2", "strip3"])
+@pytest.mark.parametrize("C,B,H,W", [(48, 1, 37, 45), (64, 2, 20, 33), (96, 1, 21, 40), (192, 1, 9, 40), (384, 1, 9, 33)])
+def test_exact_wgrad_tile(C, B, H, W, cfg):
+    """ssa_conv2d_wgrad_tile + reduce at the default split and at strips of 1, 2, 3 tiles per workgroup."""
+    _exact_wgrad("tile", B, H, W, C, C, 3, 1, 1, cfg)
+
+
+@pytest.mark.parametrize("cfg", [-1, 1], ids=["default", "strip1"])
+@pytest.mark.parametrize("B,H,W,Cin,Cout,k,stride,pad", [(1, 20, 24, 48, 96, 3, 2, 1), (2, 9, 13, 64, 40, 1, 1, 0),
+                                                          (1, 12, 16, 72, 88, 3, 1, 1), (1, 19, 1, 128, 64, 1, 1, 0)])
+def test_exact_wgrad_splitk(B, H, W, Cin, Cout, k, stride, pad, cfg):
+    """The split-K ssa_conv2d_wgrad + reduce (strided 3x3, 1x1, ragged channel counts, a one-pixel-wide image), and the
+    bias gradient beside it: ssa_colsum_bf16 of the same dy, fp32, exact."""
+    import ctypes
+    from semseg_amd._lib import check
+    _exact_wgrad("wgrad", B, H, W, Cin, Cout, k, stride, pad, cfg)
+    hb = _hb()
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    dy = ints((B, Ho, Wo, Cout), -3, 3, 43)
+    gg = guarded_copy(dy.to(ACT_DTYPE), DEV, Cout + 8)
+    out, scratch = guarded((Cout,), torch.float32, DEV), guarded((2 * Cout,), torch.float64, DEV)
+    check(hb.lib().ssa_colsum_bf16(hb._p(gg.view), B * Ho * Wo, Cout, Cout + 8, hb._p(out.view), hb._p(scratch.view), hb._s()),
+          "ssa_colsum_bf16")
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    assert_bits_equal("bias gradient", out.view.cpu(), dy.double().view(-1, Cout).sum(0).float())
+    assert_guard_intact("bias gradient", gg, out, scratch)
+
+
+@pytest.mark.skipif(bool(os.environ.get("SSA_EMU")), reason="16,384 pixels at >= 128 channels: GPU only")
+@pytest.mark.parametrize("B,H,W,Cin,Cout,k", [(1, 130, 131, 192, 200, 3), (2, 96, 100, 256, 72, 1), (1, 128, 129, 240, 128, 3)])
+def test_exact_wgrad_head(B, H, W, Cin, Cout, k):
+    """ssa_conv2d_wgrad_head + reduce (3x3 and 1x1, ragged tiles, channel-tile tails) at the sizes it takes."""
+    _exact_wgrad("head", B, H, W, Cin, Cout, k, 1, k // 2, -1)
