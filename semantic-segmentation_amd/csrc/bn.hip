@@ -54,7 +54,7 @@ __device__ __forceinline__ void block_reduce_2x8(const float* v0, const float* v
 }
 
 // Sum of the statistics replicas of channel c ([nrep][2][C] fp64), in replica order.  The (up to 8,
-// kStatReplicas of the conv epilogues) replica loads are issued TOGETHER: a rolled loop over a run-time
+// ssa::kStatReplicas of conv_epilogue.h) replica loads are issued TOGETHER: a rolled loop over a run-time
 // nrep waits for each pair of loads in turn -- eight L2 round trips in the prologue of every workgroup
 // of every apply / backward-apply launch (11-19 us for a TWO-workgroup launch before this).
 __device__ __forceinline__ void replica_sums(const double* __restrict__ sums, int nrep, int C, int c,

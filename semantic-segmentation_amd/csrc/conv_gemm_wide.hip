@@ -24,7 +24,7 @@
 //   * the filter is conv_halo_gemm.hip's: MFMA-fragment order [n-block][k-step][lane][8] (ssa_pack_filter mode 2 / 3).
 // Cin need only be a multiple of 16: the last 32-channel stage of Cin = 720 fetches zero pieces for channels >= Cin
 // (and a clamped, finite filter block: 0 * w = 0).
-#include "common.h"
+#include "conv_epilogue.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
 
@@ -34,8 +34,6 @@
 #endif
 
 namespace {
-
-constexpr int kStatReplicasW = 8;   // must equal conv_tile.hip's kStatReplicas
 
 __device__ uint4 g_zero_piece_w;    // 16 zero bytes: what a piece outside the tile / past Cin loads
 
@@ -208,55 +206,15 @@ struct ConvGemmWide1 {
   const int ldy = a.ldy, Cout = a.Cout;
   bf16_t* Cs = reinterpret_cast<bf16_t*>(smem);
   float* red = reinterpret_cast<float*>(smem + (size_t)BM * LDC * 2);       // [2 wm][2][256]
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int col = wn * 64 + ni * 32 + (lane & 31);
-    const int n = nb0 * 32 + col;
-    const float bv = (bias != nullptr && n < Cout) ? bias[n] : 0.f;
-    float sacc = 0.f, qacc = 0.f;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (wm * 4 + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const bf16_t o = f2bf(acc[mi][ni][r] + bv);
-        Cs[row * LDC + col] = o;
-        if (stats != nullptr) {
-          const float f = (p0 + row < P) ? bf2f(o) : 0.f;
-          sacc += f;
-          qacc += f * f;
-        }
-      }
-    if (stats != nullptr) {
-      sacc += __shfl_xor(sacc, 32, 64);
-      qacc += __shfl_xor(qacc, 32, 64);
-      if (lane < 32) {
-        red[(wm * 2 + 0) * 256 + col] = sacc;
-        red[(wm * 2 + 1) * 256 + col] = qacc;
-      }
-    }
-  }
+  ssa::epi_stage<LDC>(acc, bias, stats != nullptr, wm * 128, wn * 64, nb0 * 32, Cout, Cs, lane,
+                      [&](int row) { return p0 + row < P; }, ssa::EpiRedSink<NB * 32>{red, wm});
   __syncthreads();
-  if (stats != nullptr) {
-    double* st = stats + (long)(bx % kStatReplicasW) * 2 * Cout;
-    const int which = tid >> 8, col = tid & 255;
-    const int n = nb0 * 32 + col;
-    if (n < Cout) atomicAdd(&st[which * Cout + n], (double)(red[(0 * 2 + which) * 256 + col] + red[(1 * 2 + which) * 256 + col]));
-  }
+  if (stats != nullptr) ssa::epi_reduce_stats<2, NB * 32, NT>(red, stats, bx, nb0 * 32, Cout, tid);
   bf16_t* yb = reinterpret_cast<bf16_t*>(a.y);
-  constexpr int CPR = NB * 4;                    // 16-byte pieces per tile row
-  for (int idx = tid; idx < BM * CPR; idx += NT) {
-    const int row = idx / CPR, cp = idx - row * CPR;
-    const int n = nb0 * 32 + cp * 8;
-    if (p0 + row >= P || n >= Cout) continue;
-    bf16_t* dst = yb + (p0 + row) * ldy + n;
-    const bf16_t* src = Cs + row * LDC + cp * 8;
-    if (n + 8 <= Cout) {
-      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-    } else {
-      for (int j = 0; n + j < Cout; ++j) dst[j] = src[j];
-    }
-  }
+  ssa::epi_store_rows<BM, NB * 32, NT>(Cs, nb0 * 32, Cout, tid, [&](int row, bf16_t*& p) {
+    p = yb + (p0 + row) * ldy;
+    return p0 + row < P;
+  });
   }
 };
 
@@ -285,8 +243,7 @@ int ssa_conv2d_gemm_wide(const ssa_conv_desc* dp, const void* x, const void* w_f
                          void* y, double* stats, void* stream) {
   if (!dp || !x || !w_frag || !y) return SSA_EINVAL;
   if (!wide_shape_ok(dp)) return SSA_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_frag)) & 15u)
-    return SSA_EINVAL;
+  if (!ssa::conv_ptrs_ok(x, y, w_frag)) return SSA_EINVAL;
   const ssa_conv_desc& d = *dp;
   WideArgs a;
   a.x = (const bf16_t*)x; a.wfrag = (const uint4*)w_frag; a.bias = bias; a.y = y; a.stats = stats;

@@ -10,14 +10,12 @@
 // chunk's input tile is staged in LDS through registers, the filter in
 // MFMA-fragment order ([n-block][k-step][lane][8], ssa_pack_filter mode 2/3)
 // arrives by global_load_lds_dwordx4; both are double buffered.
-#include "common.h"
+#include "conv_epilogue.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
 #include <stdlib.h>
 
 namespace {
-
-constexpr int kStatReplicasG = 8;   // must equal conv_tile.hip's kStatReplicas
 
 struct HaloArgs {
   const bf16_t* x; const uint4* wfrag; const float* bias; void* y; double* stats;
@@ -29,7 +27,7 @@ struct HaloArgs {
 struct HaloTile { int bx, nb0, b, y0, x0, wm, wn; };
 
 __device__ __forceinline__ void halo_epilogue(const HaloArgs& a, const HaloTile& k, f32x16_t (&acc)[2][2], unsigned char* smem) {
-  constexpr int NB = 4, TW = 32, BM = 256;
+  constexpr int NB = 4, TW = 32, BM = 256, BN = NB * 32;
   const float* __restrict__ bias = a.bias;
   void* __restrict__ yv = a.y;
   double* __restrict__ stats = a.stats;
@@ -47,71 +45,26 @@ __device__ __forceinline__ void halo_epilogue(const HaloArgs& a, const HaloTile&
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = (wm * 2 + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const int row = (wm * 2 + mi) * 32 + ssa::acc_row(r, lane);
           const int oy = y0 + row / TW, ox = x0 + row % TW;
           if (oy < H && ox < W && n < Cout) y[((long)oy * W + ox) * ldy + n] = acc[mi][ni][r] + bv;
         }
     }
     return;
   }
-  constexpr int LDC = NB * 32 + 8;
+  constexpr int LDC = BN + 8;
   bf16_t* Cs = reinterpret_cast<bf16_t*>(smem);
   float* red = reinterpret_cast<float*>(smem + (size_t)BM * LDC * 2);   // [4 wm][2][128]
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int col = wn * 64 + ni * 32 + (lane & 31);
-    const int n = nb0 * 32 + col;
-    const float bv = (bias != nullptr && n < Cout) ? bias[n] : 0.f;
-    float sacc = 0.f, qacc = 0.f;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (wm * 2 + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const bf16_t o = f2bf(acc[mi][ni][r] + bv);
-        Cs[row * LDC + col] = o;
-        if (stats != nullptr) {
-          const float f = (y0 + row / TW < H && x0 + row % TW < W) ? bf2f(o) : 0.f;
-          sacc += f;
-          qacc += f * f;
-        }
-      }
-    if (stats != nullptr) {
-      sacc += __shfl_xor(sacc, 32, 64);
-      qacc += __shfl_xor(qacc, 32, 64);
-      if (lane < 32) {
-        red[(wm * 2 + 0) * 128 + col] = sacc;
-        red[(wm * 2 + 1) * 128 + col] = qacc;
-      }
-    }
-  }
+  ssa::epi_stage<LDC>(acc, bias, stats != nullptr, wm * 64, wn * 64, nb0 * 32, Cout, Cs, lane,
+                      [&](int row) { return y0 + row / TW < H && x0 + row % TW < W; }, ssa::EpiRedSink<BN>{red, wm});
   __syncthreads();
-  if (stats != nullptr) {
-    double* st = stats + (long)(bx % kStatReplicasG) * 2 * Cout;
-    if (tid < 256) {
-      const int which = tid >> 7, col = tid & 127;
-      const int n = nb0 * 32 + col;
-      if (n < Cout) {
-        const float v = (red[(0 * 2 + which) * 128 + col] + red[(1 * 2 + which) * 128 + col]) +
-                        (red[(2 * 2 + which) * 128 + col] + red[(3 * 2 + which) * 128 + col]);
-        atomicAdd(&st[which * Cout + n], (double)v);
-      }
-    }
-  }
+  if (stats != nullptr) ssa::epi_reduce_stats<4, BN, 512>(red, stats, bx, nb0 * 32, Cout, tid);
   bf16_t* yb = reinterpret_cast<bf16_t*>(yv) + (long)b * H * W * ldy;
-  constexpr int CPR = NB * 4;
-  for (int idx = tid; idx < BM * CPR; idx += 512) {
-    const int row = idx / CPR, cp = idx - row * CPR;
-    const int oy = y0 + row / TW, ox = x0 + row % TW, n = nb0 * 32 + cp * 8;
-    if (oy >= H || ox >= W || n >= Cout) continue;
-    bf16_t* dst = yb + ((long)oy * W + ox) * ldy + n;
-    const bf16_t* src = Cs + row * LDC + cp * 8;
-    if (n + 8 <= Cout) {
-      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-    } else {
-      for (int j = 0; n + j < Cout; ++j) dst[j] = src[j];
-    }
-  }
+  ssa::epi_store_rows<BM, BN, 512>(Cs, nb0 * 32, Cout, tid, [&](int row, bf16_t*& p) {
+    const int oy = y0 + row / TW, ox = x0 + row % TW;
+    p = yb + ((long)oy * W + ox) * ldy;
+    return oy < H && ox < W;
+  });
 }
 
 // 1x1 convs: a stage is a whole chunk -- 32 KiB of input tile + 16 KiB of filter per 12..16 MFMAs per wave, the
@@ -129,10 +82,7 @@ struct ConvHaloGemm1 {
   static __device__ __forceinline__ void run(const Args& a, const int bx, const int by, const int /*gx*/) {
   const bf16_t* __restrict__ x = a.x;
   const uint4* __restrict__ wfrag = a.wfrag;
-  const float* __restrict__ bias = a.bias;
-  void* __restrict__ yv = a.y;
-  double* __restrict__ stats = a.stats;
-  const int ldx = a.ldx, Cin = a.Cin, ldy = a.ldy, out_f32 = a.out_f32, H = a.H, W = a.W, Cout = a.Cout;
+  const int ldx = a.ldx, Cin = a.Cin, H = a.H, W = a.W;
   const int nb_total = a.nb_total, tiles_x = a.tiles_x, tiles_y = a.tiles_y;
   constexpr int NB = 4, TW = 32, TH = 8, R = KS / 2;
   constexpr int HW_ = TW + 2 * R, HH_ = TH + 2 * R;
@@ -279,12 +229,6 @@ int launch_halo1(const ssa_conv_desc& d, const void* x, const void* wfrag, const
   return launch_halo<ConvHaloGemm1<CK>>(d, 2 * halo + 2 * bst, x, wfrag, bias, y, stats, s);
 }
 
-int pick_ck(int Cin) {
-  if (Cin % 64 == 0) return 64;
-  if (Cin % 48 == 0) return 48;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -299,15 +243,14 @@ int ssa_conv2d_halo_supported(const ssa_conv_desc* d) {
   // conv_tile / the K-pipelined igemm, which spread them over more workgroups
   if (d->Cin < 192 || d->Cout < 64 || d->W < 32 || (long)d->B * d->H * d->W < 16384) return 0;
   if (d->KH == 3) return ssa_conv2d_halo_reg_supported(d);
-  return pick_ck(d->Cin) != 0;
+  return ssa::pick_ck(d->Cin) != 0;
 }
 
 int ssa_conv2d_halo(const ssa_conv_desc* dp, const void* x, const void* w_frag, const float* bias,
                     void* y, double* stats, void* stream) {
   if (!dp || !x || !w_frag || !y) return SSA_EINVAL;
   if (!ssa_conv2d_halo_supported(dp)) return SSA_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_frag)) & 15u)
-    return SSA_EINVAL;
+  if (!ssa::conv_ptrs_ok(x, y, w_frag)) return SSA_EINVAL;
   if (stats && dp->out_f32) return SSA_EINVAL;
   const ssa_conv_desc& d = *dp;
   hipStream_t s = (hipStream_t)stream;
@@ -315,7 +258,7 @@ int ssa_conv2d_halo(const ssa_conv_desc* dp, const void* x, const void* w_frag, 
   static const bool wide_on = !(getenv("SSA_GEMM_WIDE") && atoi(getenv("SSA_GEMM_WIDE")) == 0);
   if (wide_on && d.KH == 1 && ssa_conv2d_gemm_wide_supported(dp)) return ssa_conv2d_gemm_wide(dp, x, w_frag, bias, y, stats, stream);
   if (d.KH == 3) return ssa_conv2d_halo_reg(dp, x, w_frag, bias, y, stats, stream);
-  if (pick_ck(d.Cin) == 64) return launch_halo1<64>(d, x, w_frag, bias, y, stats, s);
+  if (ssa::pick_ck(d.Cin) == 64) return launch_halo1<64>(d, x, w_frag, bias, y, stats, s);
   return launch_halo1<48>(d, x, w_frag, bias, y, stats, s);
 }
 

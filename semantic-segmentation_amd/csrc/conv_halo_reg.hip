@@ -20,7 +20,7 @@
 //     workgroups per CU with independent barriers (8 waves per CU, 256 registers each).
 // Pieces outside the image are never fetched: both halo buffers are zeroed once and the DMA of such a piece is masked
 // off (EXEC), so the slot keeps its zeros for every chunk.
-#include "common.h"
+#include "conv_epilogue.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
 #include <stdlib.h>
@@ -31,8 +31,6 @@
 #endif
 
 namespace {
-
-constexpr int kStatReplicasR = 8;   // must equal conv_tile.hip's kStatReplicas
 
 struct HaloRegArgs {
   const bf16_t* x; const uint4* wfrag; const float* bias; bf16_t* y; double* stats;
@@ -226,63 +224,29 @@ struct ConvHaloReg3 {
   double* __restrict__ stats = a.stats;
   const int ldy = a.ldy, Cout = a.Cout;
   bf16_t* Cs = reinterpret_cast<bf16_t*>(smem);
-  double* st = stats ? stats + (long)(bx % kStatReplicasR) * 2 * Cout : nullptr;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int col = wn * 64 + ni * 32 + (lane & 31);
-    const int n = nb0 * 32 + col;
-    const float bv = (bias != nullptr && n < Cout) ? bias[n] : 0.f;
-    float sacc = 0.f, qacc = 0.f;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const bf16_t o = f2bf(acc[mi][ni][r] + bv);
-        Cs[row * LDC + col] = o;
-        if (stats != nullptr) {
-          const float f = (y0 + row / TW < H && x0 + row % TW < W) ? bf2f(o) : 0.f;
-          sacc += f;
-          qacc += f * f;
-        }
-      }
-    if (stats != nullptr) {
-      sacc += __shfl_xor(sacc, 32, 64);
-      qacc += __shfl_xor(qacc, 32, 64);
-      if (lane < 32 && n < Cout) {
-        atomicAdd(&st[n], (double)sacc);
-        atomicAdd(&st[Cout + n], (double)qacc);
-      }
-    }
-  }
+  double* st = stats ? stats + (long)(bx % ssa::kStatReplicas) * 2 * Cout : nullptr;
+  ssa::epi_stage<LDC>(acc, bias, stats != nullptr, 0, wn * 64, nb0 * 32, Cout, Cs, lane,
+                      [&](int row) { return y0 + row / TW < H && x0 + row % TW < W; },
+                      [&](int, int n, float sv, float qv) {
+                        if (n < Cout) {
+                          atomicAdd(&st[n], (double)sv);
+                          atomicAdd(&st[Cout + n], (double)qv);
+                        }
+                      });
   __syncthreads();
   bf16_t* yb = a.y + (long)b * H * W * ldy;
-  constexpr int CPR = NB * 4;                    // 16-byte pieces per tile row
-  for (int idx = tid; idx < BM * CPR; idx += NT) {
-    const int row = idx / CPR, cp = idx - row * CPR;
-    const int oy = y0 + row / TW, ox = x0 + row % TW, n = nb0 * 32 + cp * 8;
-    if (oy >= H || ox >= W || n >= Cout) continue;
-    bf16_t* dst = yb + ((long)oy * W + ox) * ldy + n;
-    const bf16_t* src = Cs + row * LDC + cp * 8;
-    if (n + 8 <= Cout) {
-      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-    } else {
-      for (int j = 0; n + j < Cout; ++j) dst[j] = src[j];
-    }
-  }
+  ssa::epi_store_rows<BM, NB * 32, NT>(Cs, nb0 * 32, Cout, tid, [&](int row, bf16_t*& p) {
+    const int oy = y0 + row / TW, ox = x0 + row % TW;
+    p = yb + ((long)oy * W + ox) * ldy;
+    return oy < H && ox < W;
+  });
   }
 };
-
-int pick_ck(int Cin) {
-  if (Cin % 64 == 0) return 64;
-  if (Cin % 48 == 0) return 48;
-  return 0;
-}
 
 bool reg_shape_ok(const ssa_conv_desc* d) {
   if (!d || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->dil != 1 || d->transposed || d->pad != 1) return false;
   if (d->Ho != d->H || d->Wo != d->W || d->out_f32) return false;
-  if (d->ldx % 8 || d->Cout % 8 || d->ldy % 8 || pick_ck(d->Cin) == 0) return false;
+  if (d->ldx % 8 || d->Cout % 8 || d->ldy % 8 || ssa::pick_ck(d->Cin) == 0) return false;
   // halo pieces are addressed by 32-bit byte offsets from the image's first element
   return (long)d->H * d->W * d->ldx * 2 < (1L << 32);
 }
@@ -297,8 +261,7 @@ int ssa_conv2d_halo_reg(const ssa_conv_desc* dp, const void* x, const void* w_fr
                         void* y, double* stats, void* stream) {
   if (!dp || !x || !w_frag || !y) return SSA_EINVAL;
   if (!reg_shape_ok(dp)) return SSA_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_frag)) & 15u)
-    return SSA_EINVAL;
+  if (!ssa::conv_ptrs_ok(x, y, w_frag)) return SSA_EINVAL;
   const ssa_conv_desc& d = *dp;
   HaloRegArgs a;
   a.x = (const bf16_t*)x; a.wfrag = (const uint4*)w_frag; a.bias = bias; a.y = (bf16_t*)y; a.stats = stats;
@@ -306,7 +269,7 @@ int ssa_conv2d_halo_reg(const ssa_conv_desc* dp, const void* x, const void* w_fr
   a.nb_total = (d.Cout + 31) / 32;
   a.tiles_x = (d.W + 31) / 32; a.tiles_y = (d.H + 3) / 4;
   const int gx = a.tiles_x * a.tiles_y * d.B, gy = (a.nb_total + 7) / 8;
-  if (pick_ck(d.Cin) == 64) {
+  if (ssa::pick_ck(d.Cin) == 64) {
     typedef ConvHaloReg3<64> K;
     return ssa::submit<K>(a, gx, gy, K::LDS_BYTES, (hipStream_t)stream);
   }

@@ -20,7 +20,7 @@
 // LDS is double buffered with the next stage's global loads issued before the
 // current stage's MFMAs.  LDS rows are padded to 80 bytes so the 16 lanes that
 // ds_read_b128 services together hit 16 distinct 16-byte slots.
-#include "common.h"
+#include "conv_epilogue.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
 #include <limits.h>
@@ -238,7 +238,7 @@ struct ConvIgemm {
         const float bv = (bias != nullptr && n < d.Cout) ? bias[n] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = wm * MI * 32 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const int row = wm * MI * 32 + mi * 32 + ssa::acc_row(r, lane);
           const int m = m0 + row;
           if (m < M && n < d.Cout) y[opix(m) * d.ldy + n] = acc[mi][ni][r] + bv;
         }
@@ -258,7 +258,7 @@ struct ConvIgemm {
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wm * MI * 32 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = wm * MI * 32 + mi * 32 + ssa::acc_row(r, lane);
         const bf16_t o = f2bf(acc[mi][ni][r] + bv);
         Cs[row * LDC + col] = o;
         if (stats != nullptr) {          // batch statistics of the bf16-rounded outputs (fused bn_stats)
@@ -278,19 +278,8 @@ struct ConvIgemm {
     }
   }
   __syncthreads();
-  if (stats != nullptr) {
-    double* st = stats + (long)(bx % 8) * 2 * d.Cout;     // replica, as conv_tile.hip
-    for (int i = tid; i < 2 * BN; i += NT) {
-      const int which = i / BN, col = i - which * BN;
-      const int n = n0 + col;
-      if (n < d.Cout) {
-        float v = 0.f;
-#pragma unroll
-        for (int w_ = 0; w_ < WGM; ++w_) v += red[(w_ * 2 + which) * BN + col];
-        atomicAdd(&st[which * d.Cout + n], (double)v);
-      }
-    }
-  }
+  // (this kernel adds its wave rows' sums left to right, not as the tree of the other kernels: another fp32 rounding)
+  if (stats != nullptr) ssa::epi_reduce_stats<WGM, BN, NT, false>(red, stats, bx, n0, d.Cout, tid);
   bf16_t* y = reinterpret_cast<bf16_t*>(yv);
   constexpr int CPR = BN / 8;
   for (int idx = tid; idx < BM * CPR; idx += NT) {
@@ -510,7 +499,7 @@ struct ConvWgradTr {
       const int kcol = n0 + wn * NI * 32 + ni * 32 + (lane & 31);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = m0 + wm * MI * 32 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int co = m0 + wm * MI * 32 + mi * 32 + ssa::acc_row(r, lane);
         if (co < cout_pad && kcol < Kflat) out[(long)co * Kflat + kcol] = acc[mi][ni][r];
       }
     }

@@ -36,14 +36,12 @@
 // Group-aware (group.h): inside an ssa_group_begin/ssa_group_end bracket the launches of the
 // independent problems of one depth level (branches x scale passes) that share a kernel
 // instantiation become one launch.
-#include "common.h"
+#include "conv_epilogue.h"
 #include "group.h"
 #include <stdlib.h>
 #include "../../include/semseg_hip.h"
 
 namespace {
-
-constexpr int kStatReplicas = 8;   // BN partial sums are spread over 8 replicas (atomic contention)
 
 // Filter stage (channel chunk cc, taps [tap0, tap0+TPC)) of the NB n-blocks -> LDS
 // buffer, as direct global->LDS DMA: one global_load_lds_dwordx4 per wave moves one
@@ -249,7 +247,7 @@ struct ConvTile {
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (wave * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = (wave * MI + mi) * 32 + ssa::acc_row(r, lane);
         bf16_t o = f2bf(acc[mi][nb][r] + bv);
         if constexpr (AUX) {
           const float xv = bf2f(Xs[row * LDC + col]);
@@ -282,33 +280,14 @@ struct ConvTile {
     }
   }
   __syncthreads();
-  if (stats != nullptr) {
-    // stats layout: [replica][2][C]; replica = workgroup index mod kStatReplicas
-    double* st = stats + (long)(bx % kStatReplicas) * 2 * Cout;
-    for (int i = tid; i < 2 * NB * 32; i += 256) {
-      const int which = i / (NB * 32), col = i - which * NB * 32;
-      const int n = nb0 * 32 + col;
-      if (n < Cout) {
-        const float v = (red[(0 * 2 + which) * NB * 32 + col] + red[(1 * 2 + which) * NB * 32 + col]) +
-                        (red[(2 * 2 + which) * NB * 32 + col] + red[(3 * 2 + which) * NB * 32 + col]);
-        atomicAdd(&st[which * Cout + n], (double)v);
-      }
-    }
-  }
+  if (stats != nullptr) ssa::epi_reduce_stats<4, NB * 32, 256>(red, stats, bx, nb0 * 32, Cout, tid);
   bf16_t* yb = y + (long)b * H * W * ldy;
-  for (int idx = tid; idx < BM * CPR; idx += 256) {
-    const int row = idx / CPR, cp = idx - row * CPR;
+  ssa::epi_store_rows<BM, NB * 32, 256>(Cs, nb0 * 32, Cout, tid, [&](int row, bf16_t*& p) {
     const int ty = row / TW, tx = row - ty * TW;
-    const int oy = y0 + ty, ox = x0 + tx, n = nb0 * 32 + cp * 8;
-    if (oy >= H || ox >= W || n >= Cout) continue;
-    bf16_t* dst = yb + ((long)oy * W + ox) * ldy + n;
-    const bf16_t* src = Cs + row * LDC + cp * 8;
-    if (n + 8 <= Cout) {
-      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-    } else {
-      for (int j = 0; n + j < Cout; ++j) dst[j] = src[j];
-    }
-  }
+    const int oy = y0 + ty, ox = x0 + tx;
+    p = yb + ((long)oy * W + ox) * ldy;
+    return oy < H && ox < W;
+  });
   }
 };
 
@@ -366,8 +345,7 @@ int tile_impl(const ssa_conv_desc* dp, const void* x, const void* w_frag, const 
               double* stats, const AuxArgs& ax, void* stream) {
   if (!dp || !x || !w_frag || !y) return SSA_EINVAL;
   if (!ssa_conv2d_tile_supported(dp)) return SSA_EUNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_frag)) & 15u)
-    return SSA_EINVAL;
+  if (!ssa::conv_ptrs_ok(x, y, w_frag)) return SSA_EINVAL;
   const ssa_conv_desc& d = *dp;
   hipStream_t s = (hipStream_t)stream;
   switch (d.Cin) {
@@ -409,6 +387,6 @@ int ssa_conv2d_tile_aux(const ssa_conv_desc* dp, const void* x, const void* w_fr
   return tile_impl(dp, x, w_frag, bias, y, stats, AuxArgs{aux, ldaux, coef, aux_mode}, stream);
 }
 
-int ssa_bn_stat_replicas(void) { return kStatReplicas; }
+int ssa_bn_stat_replicas(void) { return ssa::kStatReplicas; }
 
 }  // extern "C"

@@ -31,14 +31,12 @@
 // units of ~3,800 clocks.
 // Epilogues (as conv_tile.hip): BatchNorm batch statistics; aux_mode 1: + residual gradient; aux_mode 2: bn1's
 // backward sums from (x tile, dz).  (Round 3's BatchNorm-in-the-staging fold was measured slower and is gone.)
-#include "common.h"
+#include "conv_epilogue.h"
 #include "group.h"
 #include <stdlib.h>
 #include "../../include/semseg_hip.h"
 
 namespace {
-
-constexpr int kStatReplicas = 8;   // as conv_tile.hip (ssa_bn_stat_replicas)
 
 #ifdef SSA_TILE_TIMING
 #define SSA_STAMP(k) do { if (tdbg && it < 24) { tlds[it * 8 + (k)] = (long)__builtin_amdgcn_s_memtime(); } } while (0)
@@ -485,7 +483,7 @@ struct ConvTileP {
           }
       }
       __syncthreads();
-      double* st = stats + (long)(strip % kStatReplicas) * 2 * Cout;
+      double* st = stats + (long)(strip % ssa::kStatReplicas) * 2 * Cout;
       if (tid < NB * 32) {
         const int n = nb0 * 32 + tid;
         if (n < Cout) {
@@ -565,8 +563,7 @@ int ssa_conv2d_tile_p(const ssa_conv_desc* dp, const void* x, const void* w_frag
                       double* stats, const void* aux, int ldaux, const float* coef, int aux_mode, void* stream) {
   if (!dp || !x || !w_frag || !y) return SSA_EINVAL;
   if (!ssa_conv2d_tile_p_supported(dp) || bias) return SSA_EUNSUPPORTED;   // the trunk convs have no bias (hrnetv2.py:31-34)
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_frag)) & 15u)
-    return SSA_EINVAL;
+  if (!ssa::conv_ptrs_ok(x, y, w_frag)) return SSA_EINVAL;
   if (aux_mode < 0 || aux_mode > 4) return SSA_EINVAL;
   // 3 / 4: the conv's inference BatchNorm as the epilogue (coef = its [4][Cout] table), 4 with the ReLU; aux = the
   // residual tile or NULL

@@ -14,12 +14,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the emulated share of the exact tests: every strip regime once (ragged, image crossing, tiles_x == 1, interior + border,
-# one strip over the whole problem, the units < nchunk clamp), every epilogue mode, both filter packings
+# one strip over the whole problem, the units < nchunk clamp), every epilogue mode, both filter packings; of the head
+# kernels the small wide-GEMM cases and the one 256 x 128 halo-GEMM case that runs in seconds
 _EXACT = ("exact_strip and (need_rounding or sliced or grouped or mode0[c48u4-fwd or mode0[c48u64-dgrad or mode0[c48w20-fwd "
           "or mode0[c96u5-fwd or mode0[c192u16-dgrad or mode0[c384u4-fwd or no_stats[c48w16 or mode1[c48u5-dgrad "
           "or mode2[c48u4 or mode2[c192u12 or affine[c48u3-res-mode4relu "
           "or affine[c48w16-res-mode3 or affine[c48u5-nores-mode4relu) or exact_tile_and_tile_aux or exact_wgrad_splitk "
-          "or exact_gemm_wide or exact_dgrad_s2 and (case2 or case4 or case5) "
+          "or exact_gemm_wide or exact_halo_gemm_1x1[A or exact_dgrad_s2 and (case2 or case4 or case5) "
           "or exact_igemm and 3-out16 or exact_wgrad_tile and 48-1-37-45-strip2")
 
 _EXACT_F16 = ("exact_strip and (need_rounding or mode0[c48u4-fwd or mode1[c48u5-dgrad or mode2[c48u4 "
@@ -39,7 +40,7 @@ SELECTION = [
     ("tests/test_kernels_gpu.py", _EXACT),
 ]
 # how many tests an expression must run: a renamed case id would otherwise silently select fewer
-MIN_PASSED = {_EXACT: 46, _EXACT_F16: 10}
+MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10}
 
 
 # (file, -k expression, extra environment): the fp16-storage build of the same kernels (its own rounding helpers)

@@ -1544,6 +1544,61 @@ def test_exact_gemm_wide_1x1(case):
     hb.clear_pack_cache()
 
 
+HALO_GEMM_EXACT_CASES = [
+    # id, B, H, W, Cin, Cout, bias, stats, transposed-pack, |x| <=, |w| <=, fp32 output.  ssa_conv2d_halo keeps a 1x1
+    # problem for its own 256 x 128 kernel at Cin >= 192, Cout >= 64, W >= 32, B*H*W >= 16384 unless the wide kernel
+    # wants it (Cout > 256): the smallest shapes that pass the dispatcher and still reach the kernel's edges.
+    ("A", 1, 130, 127, 192, 72, True, True, False, 1, 2, False),     # CK 64, ragged tile rows and columns, n-block tail
+    ("B", 2, 96, 88, 240, 136, False, True, True, 1, 2, False),      # CK 48, second channel tile 8 wide, batch 2, dgrad packing
+    ("C", 1, 128, 128, 256, 200, True, False, False, 4, 4, False),   # outputs in the thousands: the rounding decides bits
+    ("D", 1, 128, 128, 192, 65, True, False, False, 4, 4, True),     # the fp32 branch of the logit convs, odd channel count
+]
+
+
+@pytest.mark.parametrize("case", HALO_GEMM_EXACT_CASES, ids=[c[0] for c in HALO_GEMM_EXACT_CASES])
+def test_exact_halo_gemm_1x1(case):
+    """ConvHaloGemm1 (csrc/conv_halo_gemm.hip) through ssa_conv2d_halo, integer operands: bits of the 16-bit output and
+    sums of the stats (A, B: sum of y^2 per channel stays below 2^24; C, D carry no stats because theirs does not), and
+    the fp32 output of the 64-255-class logit convs, an exact integer, against the fp32 reference (D)."""
+    import ctypes
+    from semseg_amd._lib import check
+    hb = _hb()
+    name, B, H, W, Cin, Cout, bias, stats, tr, ax, aw, out_f32 = case
+    x, w = ints((B, Cin, H, W), -ax, ax, 3), ints((Cout, Cin, 1, 1), -aw, aw, 4)
+    b = ints((Cout,), -5, 5, 5) if bias else None
+    ref = conv_ref64(x, w, b, 1, 0, 1).permute(0, 2, 3, 1).contiguous()
+    nrep = not_representable(ref)
+    print("[exact halo_gemm %s] %d outputs not representable" % (name, nrep))
+    if name == "C" and ACT_DTYPE == torch.bfloat16:
+        assert nrep > 0
+    hb.clear_pack_cache()
+    xg = guarded_copy(nhwc(x).to(ACT_DTYPE), DEV)
+    if tr:
+        keep = w[:, :, 0, 0].t().contiguous().view(Cin, Cout, 1, 1).to(DEV)
+        wp, _ = hb._packed_filter(keep, 3, 0, Cin)
+    else:
+        keep = w.to(DEV)
+        wp, _ = hb._packed_filter(keep, 2, Cin, 0)
+    d = hb._tile_desc(B, H, W, Cin, Cin, Cout, (1, 1), 1, 0, 1, H, W, out_f32)
+    L = hb.lib()
+    assert L.ssa_conv2d_halo_supported(ctypes.byref(d)) == 1
+    assert L.ssa_conv2d_gemm_wide_supported(ctypes.byref(d)) == 0
+    yg, sg = guarded((B, H, W, Cout), torch.float32 if out_f32 else ACT_DTYPE, DEV), _stats_buf(hb, Cout, stats)
+    bd = b.to(DEV) if b is not None else None
+    check(L.ssa_conv2d_halo(ctypes.byref(d), hb._p(xg.view), hb._p(wp), hb._p(bd), hb._p(yg.view),
+                            hb._p(sg.view) if sg else None, hb._s()), "halo")
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    if out_f32:
+        want = ref.float()
+        assert torch.equal(want.double(), ref)
+        assert_bits_equal("halo_gemm %s fp32" % name, yg.view.cpu(), want)
+        assert_guard_intact("halo_gemm %s fp32" % name, yg)
+    else:
+        _exact_fwd_check("halo_gemm %s" % name, yg, sg, ref, Cout)
+    hb.clear_pack_cache()
+
+
 @pytest.mark.parametrize("out_f32", [False, True], ids=["out16", "out32"])
 @pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5])
 def test_exact_igemm_tile_configs(cfg, out_f32):
