@@ -12,9 +12,12 @@ from util import ACT_DTYPE
 
 LIMIT = float(2 ** 24)
 
-# a NaN bit pattern per element type (quiet NaN with a payload: no kernel produces it by arithmetic)
+# a NaN bit pattern per element type (quiet NaN with a payload: no kernel produces it by arithmetic).  The integer types
+# (sign-mask bytes, num_batches_tracked) have no NaN: a fill value stands in for it -- a test must not depend on it
+# (compare inside the view only, check the surroundings with assert_guard_intact).
 _NAN_BITS = {torch.bfloat16: (torch.int16, 0x7FC1), torch.float16: (torch.int16, 0x7E01),
-             torch.float32: (torch.int32, 0x7FC00001), torch.float64: (torch.int64, 0x7FF8000000000001)}
+             torch.float32: (torch.int32, 0x7FC00001), torch.float64: (torch.int64, 0x7FF8000000000001),
+             torch.uint8: (torch.uint8, 0xA5), torch.int64: (torch.int64, 0x7FF8000000000001)}
 
 
 def ints(shape, lo, hi, seed):
@@ -68,6 +71,13 @@ def to_act(ref64):
     f = ref64.to(torch.float32)
     assert torch.equal(f.double(), ref64), "reference is not exact in fp32"
     return f.to(ACT_DTYPE)
+
+
+def to_f32(ref64):
+    """float64 -> fp32, asserted exact (the reference of an fp32 output of an exact test)."""
+    f = ref64.to(torch.float32)
+    assert torch.equal(f.double(), ref64), "reference is not exact in fp32"
+    return f
 
 
 def not_representable(ref64):
@@ -159,11 +169,75 @@ def assert_guard_intact(name, *gs):
     """The guard around every view, and the neighbouring channels of a slice, still hold the fill pattern bit for bit."""
     for g in gs:
         itype, pat = _NAN_BITS[g.buf.dtype]
-        raw = g.buf.view(itype).cpu()
-        bad = (raw != torch.tensor(pat, dtype=itype)) & ~g.inside
+        raw = g.buf.view(itype)                     # compared where the buffer lives: a device buffer may be hundreds of MB
+        bad = (raw != torch.tensor(pat, dtype=itype, device=raw.device)) & ~g.inside.to(raw.device)
         n = int(bad.sum())
         if n:
             i = int(bad.nonzero()[0])
             first_in = int(g.inside.nonzero()[0])
             raise AssertionError("%s: %d guard elements overwritten; first at buffer element %d (the view starts at %d): "
                                  "bits %#x" % (name, n, i, first_in, int(raw[i]) & ((1 << (8 * g.buf.element_size())) - 1)))
+
+
+# ---- helpers of the exact BatchNorm tests
+def pow2(shape, lo, hi, seed, signed=False):
+    """fp32 tensor of powers of two 2^k, k uniform in [lo, hi]; signed: with both signs."""
+    g = torch.Generator().manual_seed(seed)
+    v = 2.0 ** torch.randint(lo, hi + 1, tuple(shape), generator=g).float()
+    if signed:
+        v = v * (torch.randint(0, 2, tuple(shape), generator=g).float() * 2 - 1)
+    return v
+
+
+def choice(shape, values, seed):
+    """fp32 tensor drawn uniformly from `values`."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.tensor(values, dtype=torch.float32)[torch.randint(0, len(values), tuple(shape), generator=g)]
+
+
+def sign_bytes(z):
+    """The BatchNorm sign mask of z [P, C]: uint8 [P, C / 8], bit j of byte [p][c / 8] = z[p][8 (c / 8) + j] > 0."""
+    P, C = z.shape
+    assert C % 8 == 0
+    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=z.device)
+    return ((z > 0).view(P, C // 8, 8).to(torch.int32) * w).sum(2).to(torch.uint8)
+
+
+def split_replicas(total, nrep, seed, amp=2 ** 40):
+    """`total` (integer-valued float64 [..]) split over nrep replicas [nrep, ..]: integer-valued float64 pieces, large and
+    of mixed sign (|piece| up to `amp` against totals of a few thousand), whose sum -- in ANY order, every partial sum is
+    an integer far below 2^53 -- is exactly `total`."""
+    total = total.double()
+    assert torch.equal(total, total.round()) and float(total.abs().max()) < 2.0 ** 40
+    g = torch.Generator().manual_seed(seed)
+    pieces = torch.randint(-amp, amp + 1, (nrep,) + tuple(total.shape), generator=g).double()
+    pieces[nrep - 1] = total - pieces[:nrep - 1].sum(0)
+    assert torch.equal(pieces.sum(0), total) and nrep * float(amp) < 2.0 ** 52
+    if nrep > 1:        # large and of mixed sign: a replica left out or counted twice is off by far more than a rounding
+        assert float(pieces.abs().max()) > 2.0 ** 30 and bool((pieces > 0).any()) and bool((pieces < 0).any())
+    return pieces
+
+
+def split_replicas_real(total, nrep, seed, amp=2 ** 20):
+    """Real-valued float64 sums split over nrep replicas.  Returns (pieces [nrep, ..], the float64 sum of the pieces in
+    replica order 0 .. nrep-1 from 0.0 -- the order the kernels add them in, which is therefore the value the
+    reference has to start from: it differs from `total` by an fp64 rounding or two)."""
+    total = total.double()
+    g = torch.Generator().manual_seed(seed)
+    pieces = torch.randint(-amp, amp + 1, (nrep,) + tuple(total.shape), generator=g).double()
+    pieces[nrep - 1] = total - pieces[:nrep - 1].sum(0)
+    acc = torch.zeros_like(total)
+    for r in range(nrep):
+        acc = acc + pieces[r]
+    return pieces, acc
+
+
+def ulp_err32(got, ref64):
+    """|got - ref| in units of the fp32 spacing at |ref| (per element, float64): 0.5 is a correctly rounded cast.  ref = 0
+    counts the spacing of the smallest normal number."""
+    got, ref = got.detach().double().cpu(), ref64.detach().double().cpu()
+    tiny = torch.tensor(2.0 ** -126, dtype=torch.float64)
+    e = torch.floor(torch.log2(torch.maximum(ref.abs(), tiny)))
+    # log2 of an fp64 just below a power of two may round up to it: put the exponent right
+    e = torch.where(2.0 ** e > torch.maximum(ref.abs(), tiny), e - 1, e)
+    return (got - ref).abs() / 2.0 ** (e - 23)

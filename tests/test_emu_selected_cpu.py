@@ -26,6 +26,13 @@ _EXACT = ("exact_strip and (need_rounding or sliced or grouped or mode0[c48u4-fw
 _EXACT_F16 = ("exact_strip and (need_rounding or mode0[c48u4-fwd or mode1[c48u5-dgrad or mode2[c48u4 "
               "or affine[c48u3-res-mode4relu or no_stats[c48w16) or exact_tile_and_tile_aux and case3 or exact_igemm and 3-out16")
 
+# the exact BatchNorm tests (csrc/bn.hip through the C ABI): the cases of one chunk per workgroup -- VC = 1 with P < RP, the
+# ragged last range at 252 of 256 active threads, VC = 31 with a last range of one pixel -- in their full configuration
+# matrices, the parameter-gradient casts, the grid mirror, and the evaluation-mode backward (the GPU runs the multi-chunk
+# cases of 6 to 26 M elements)
+_EXACT_BN = "exact_bn and (c8 or c48 or c248 or param_grads or plan_mirror) or bn_eval_backward"
+_EXACT_BN_F16 = "exact_bn and (c48 or param_grads)"
+
 # (file, -k expression): each entry a few seconds under emulation
 SELECTION = [
     ("tests/test_kernels_gpu.py", "bce_rmi or scale_fusion or cross_entropy or sigmoid or softmax"),
@@ -38,13 +45,15 @@ SELECTION = [
     # the exact (integer-operand, bit-for-bit) conv tests: the persistent trunk kernel over multi-tile strips in every
     # epilogue mode, and the small cases of the other conv entry points (the GPU runs the full lists)
     ("tests/test_kernels_gpu.py", _EXACT),
+    ("tests/test_kernels_gpu.py", _EXACT_BN),
 ]
 # how many tests an expression must run: a renamed case id would otherwise silently select fewer
-MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10}
+MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10, _EXACT_BN: 27, _EXACT_BN_F16: 8}
 
 
 # (file, -k expression, extra environment): the fp16-storage build of the same kernels (its own rounding helpers)
-SELECTION_ENV = [("tests/test_kernels_gpu.py", _EXACT_F16, {"SSA_ACT_DTYPE": "fp16"})]
+SELECTION_ENV = [("tests/test_kernels_gpu.py", _EXACT_F16, {"SSA_ACT_DTYPE": "fp16"}),
+                 ("tests/test_kernels_gpu.py", _EXACT_BN_F16, {"SSA_ACT_DTYPE": "fp16"})]
 
 
 def _passed_enough(expr, tail):

@@ -115,3 +115,84 @@ def test_references_against_a_direct_sum():
     dw = wgrad_ref64(x, dy, 3, 1, 1, 1)
     want = sum(float(xp[b, 1, oy + 0, ox + 2] * dy[b, 3, oy, ox]) for b in range(2) for oy in range(5) for ox in range(4))
     assert float(dw[3, 1, 0, 2]) == want
+
+
+# ---- the helpers of the exact BatchNorm tests
+from exact_util import choice, pow2, sign_bytes, split_replicas, split_replicas_real, to_f32, ulp_err32  # noqa: E402
+
+
+@pytest.mark.parametrize("dtype,shape", [(torch.uint8, (7, 6)), (torch.int64, (1,)), (torch.float32, (4, 24))])
+def test_guard_of_the_integer_buffers_reports_one_overwritten_element(dtype, shape):
+    """The sign-mask bytes and num_batches_tracked have no NaN: the guard is a fill value, reported all the same."""
+    g = guarded(shape, dtype, "cpu")
+    assert g.view.shape == shape and g.view.data_ptr() % 16 == 0 and int(g.inside.sum()) == g.view.numel()
+    g.view.copy_(torch.arange(g.view.numel()).view(shape).to(dtype))
+    assert_guard_intact("clean", g)
+    first, last = int(g.inside.nonzero()[0]), int(g.inside.nonzero()[-1])
+    for where in (first - 1, last + 1):
+        saved = g.buf[where].clone()
+        g.buf[where] = 1
+        with pytest.raises(AssertionError, match="1 guard elements overwritten"):
+            assert_guard_intact("dirty", g)
+        g.buf[where] = saved
+    assert_guard_intact("restored", g)
+    got = g.view.clone()
+    assert_bits_equal("same", got, g.view)
+    got.view(-1)[got.numel() - 1] += 1
+    with pytest.raises(AssertionError, match="1 of %d elements differ" % got.numel()):
+        assert_bits_equal("one off", got, g.view)
+
+
+def test_pow2_and_choice_draw_what_they_say():
+    p = pow2((500,), -2, 2, seed=1, signed=True)
+    assert set(p.abs().tolist()) == {0.25, 0.5, 1.0, 2.0, 4.0} and (p > 0).any() and (p < 0).any()
+    assert (pow2((50,), -2, 1, seed=2) > 0).all() and torch.equal(pow2((50,), -2, 1, seed=2), pow2((50,), -2, 1, seed=2))
+    c = choice((3, 200), [0.0, 0.5, 1.0, 2.0], seed=3)
+    assert c.shape == (3, 200) and set(c.flatten().tolist()) == {0.0, 0.5, 1.0, 2.0}
+
+
+def test_sign_bytes_bit_order():
+    z = torch.zeros(2, 16)
+    z[0, 0], z[0, 3], z[0, 15], z[1, 8], z[1, 9] = 1.0, 0.5, 2.0, -1.0, 3.0          # negative and zero: bit clear
+    z[1, 1] = -0.0
+    assert sign_bytes(z).tolist() == [[0b00001001, 0b10000000], [0, 0b00000010]]
+    assert sign_bytes(z.to(ACT_DTYPE)).dtype == torch.uint8
+
+
+def test_split_replicas_sums_exactly_in_any_order():
+    total = ints((2, 40), -3000, 3000, seed=9).double() * 1024
+    assert torch.equal(split_replicas(total, 1, seed=1)[0], total)
+    for nrep in (4, 11):
+        p = split_replicas(total, nrep, seed=nrep)
+        assert p.shape == (nrep, 2, 40) and torch.equal(p, p.round())
+        assert torch.equal(p.sum(0), total) and torch.equal(p.flip(0).sum(0), total)
+        acc = torch.zeros_like(total)
+        for r in torch.randperm(nrep).tolist():
+            acc = acc + p[r]
+        assert torch.equal(acc, total)
+        assert float(p.abs().max()) > 2.0 ** 30 and (p > 0).any() and (p < 0).any()
+    with pytest.raises(AssertionError):
+        split_replicas(total + 0.5, 4, seed=0)
+    real = torch.rand(2, 40, dtype=torch.float64) * 1e5
+    p, acc = split_replicas_real(real, 11, seed=5)
+    want = torch.zeros_like(real)
+    for r in range(11):
+        want = want + p[r]
+    assert torch.equal(acc, want) and float(((acc - real).abs() / real).max()) < 1e-9
+
+
+def test_ulp_err32_counts_fp32_spacings():
+    ref = torch.tensor([1.0, 1.5, -3.0, 0.3, 2.0 ** -3, 1e-3], dtype=torch.float64)
+    f = ref.float()
+    assert float(ulp_err32(f, f.double()).max()) == 0.0
+    up = (f.view(torch.int32) + 1).view(torch.float32)                  # the next fp32 away from zero
+    e = ulp_err32(up, f.double())
+    assert torch.equal(e, torch.ones_like(e)), e
+    # a correctly rounded cast is at most half a spacing off; just below a power of two the spacing is the smaller one
+    r64 = torch.tensor([0.1, 1.0 / 3.0, 2.0 - 2.0 ** -30], dtype=torch.float64)
+    e = ulp_err32(r64.float(), r64)
+    assert float(e.max()) <= 0.5 and float(e.min()) > 0.0
+    assert float(ulp_err32(torch.tensor([2.0]), torch.tensor([2.0 - 2.0 ** -30], dtype=torch.float64))) == pytest.approx(2.0 ** -7)
+    with pytest.raises(AssertionError):
+        to_f32(torch.tensor([0.1], dtype=torch.float64))
+    assert to_f32(torch.tensor([0.375], dtype=torch.float64)).dtype == torch.float32
