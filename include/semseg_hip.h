@@ -645,6 +645,46 @@ int ssa_label_u8_crop_flip(const unsigned char* lab_hw, int H, int W, int x0, in
 int ssa_resample_u8(const unsigned char* src, int Hs, int Ws, int C, int axis, unsigned char* dst,
                     int n_out, const int* bounds, const int* coefs, int ksize, void* stream);
 
+/* ColorJitter on the device (transforms/transforms.py:192-362; built as ColorJitter(0.25, 0.25, 0.25, 0.25)
+ * by datasets/__init__.py:94-99 under the default --color_aug): the image-only augmentation between the joint
+ * crop / flip and ToTensor + Normalize, bit-identical to Pillow's ImageEnhance.Brightness / Contrast / Color
+ * and to the HSV round trip of adjust_hue (csrc/color_jitter.hip states the arithmetic).
+ * A program is up to four DISTINCT steps in application order (the order ColorJitter.get_params shuffled);
+ * factor[] is indexed by the op code of the three blend steps, hue_byte = trunc(hue_factor * 255) mod 256 is
+ * added to H.  It is a HOST struct: the entry points pass it to the kernels by value.                    */
+enum { SSA_JITTER_BRIGHTNESS = 0, SSA_JITTER_CONTRAST = 1, SSA_JITTER_SATURATION = 2, SSA_JITTER_HUE = 3 };
+typedef struct ssa_jitter_program {
+  int n_ops;        /* 0..4 */
+  int op[4];        /* SSA_JITTER_* */
+  float factor[3];  /* brightness, contrast, saturation */
+  int hue_byte;     /* 0..255 */
+} ssa_jitter_program;
+
+/* transforms/transforms.py:192-362, datasets/__init__.py:94-99 -- the sum ImageEnhance.Contrast averages:
+ * *counter = sum over the window (x0, y0, cw, ch) of img_hwc (uint8 [H][W][3] on the device) of
+ * L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16 of the pixel AFTER the steps that precede the program's
+ * contrast step.  counter: one 8-byte-aligned 64-bit DEVICE word, cleared here on the stream (by a one-thread launch).  Integer
+ * addition: exact and independent of the order.  A program without a contrast step launches nothing (counter
+ * may then be NULL).                                                                                      */
+int ssa_jitter_luma_sum(const unsigned char* img_hwc, int H, int W, int x0, int y0, int cw, int ch,
+                        const ssa_jitter_program* program, unsigned long long* counter, void* stream);
+/* transforms/transforms.py:192-362, datasets/__init__.py:94-99 -- the whole program on the window, optionally
+ * mirrored (the contrast mean does not change under the flip): out_hwc uint8 [ch][cw][3] on the device.  The
+ * contrast mean m = int(*counter / (cw * ch) + 0.5) is formed ON THE DEVICE from what ssa_jitter_luma_sum
+ * left (same window, same program, same stream): no host synchronisation between the two.               */
+int ssa_jitter_apply_u8(const unsigned char* img_hwc, int H, int W, int x0, int y0, int cw, int ch, int flip,
+                        const ssa_jitter_program* program, const unsigned long long* counter,
+                        unsigned char* out_hwc, void* stream);
+/* transforms/transforms.py:192-362, datasets/__init__.py:94-99 followed by ToTensor + Normalize
+ * (datasets/__init__.py:104-107): ssa_jitter_apply_u8 fused with the arithmetic and the NHWC [ch][cw][cpad]
+ * store of ssa_image_u8_crop_flip_normalize, in the build's 16-bit element type.  Bit-identical to the two in
+ * sequence.  All three return -1 before touching the device on a bad window, an unknown or repeated op code,
+ * a null pointer, or a program with a contrast step and no counter.                                       */
+int ssa_jitter_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, int x0, int y0, int cw, int ch,
+                                   int flip, const ssa_jitter_program* program,
+                                   const unsigned long long* counter, const float* mean3, const float* std3,
+                                   void* out_nhwc_bf16, int cpad, void* stream);
+
 /* Evaluation tail on the device (utils/trnval_utils.py:173-196 + utils/misc.py:50-67
  * fast_hist): pred[p] = first argmax_c logits[p,c] (uint8, optional) and
  * hist[gt*C + pred] += 1 for 0 <= gt < C (int64 [C*C], ACCUMULATED: clear it once per

@@ -73,6 +73,11 @@ class ConvDesc(ctypes.Structure):
         "stride", "pad", "dil", "transposed", "Kpad", "out_f32", "cfg")]
 
 
+class JitterProgram(ctypes.Structure):
+    """Mirror of ssa_jitter_program (36 bytes)."""
+    _fields_ = [("n_ops", c_int), ("op", c_int * 4), ("factor", c_float * 3), ("hue_byte", c_int)]
+
+
 _P = c_void_p
 _SIGS = {
     "ssa_version": ([], c_int),
@@ -187,6 +192,11 @@ _SIGS = {
                                          c_int),
     "ssa_resample_u8": ([_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P], c_int),
     "ssa_label_u8_crop_flip": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P], c_int),
+    "ssa_jitter_luma_sum": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P, _P], c_int),
+    "ssa_jitter_apply_u8": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P, _P, _P],
+                            c_int),
+    "ssa_jitter_crop_flip_normalize": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P,
+                                        _P, _P, _P, c_int, _P], c_int),
     "ssa_confusion_matrix": ([_P, c_int, _P, c_long, c_int, _P, _P, _P], c_int),
     "ssa_eval_tail": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P,
                        _P, _P], c_int),

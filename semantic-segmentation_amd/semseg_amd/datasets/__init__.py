@@ -3,3 +3,5 @@
 nearest-neighbour label resize."""
 from .sampler import DistributedSampler, shard_indices      # noqa: F401
 from .transforms import nearest_index_table, resize_labels_nearest   # noqa: F401
+from .transforms import (ColorJitter, JitterParams, adjust_brightness, adjust_contrast, adjust_hue,   # noqa: F401
+                         adjust_saturation, color_jitter, crop_flip_normalize)

@@ -61,9 +61,12 @@ def resize_labels_nearest(mask, size):
 MEAN_STD = ([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])      # config.py:96-97 (cfg.DATASET.MEAN / STD)
 
 
-def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD):
+def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitter=None):
     """img_u8: uint8 CUDA [H,W,3] (RGB, as np.array(PIL image)); labels_u8: uint8 CUDA [H,W] or None;
     window = (x0, y0, w, h) as PIL's crop box origin + size; flip: mirror the cropped pair.
+    jitter: None, or the JitterParams of ColorJitter.get_params -- the image-only augmentation the reference runs
+    between the joint transforms and ToTensor (datasets/base_loader.py:141-142), applied to the window in the same
+    launch that normalises it (ssa_jitter_luma_sum + ssa_jitter_crop_flip_normalize); the labels do not see it.
     Returns (image [1,h,w,16] bf16 NHWC -- hand it to the network's trunk --, labels [1,h,w] int64)."""
     from .._lib import lib, check
     assert img_u8.dtype == torch.uint8 and img_u8.is_cuda and img_u8.dim() == 3 and img_u8.shape[2] == 3
@@ -71,13 +74,16 @@ def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD):
     H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
     x0, y0, cw, ch = (int(v) for v in window)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    mean = (ctypes.c_float * 3)(*mean_std[0])
-    std = (ctypes.c_float * 3)(*mean_std[1])
-    from ..hip_backend import ACT_DTYPE
-    out = torch.empty((1, ch, cw, 16), dtype=ACT_DTYPE, device=img_u8.device)
-    check(lib().ssa_image_u8_crop_flip_normalize(ctypes.c_void_p(img_u8.data_ptr()), H, W, x0, y0, cw, ch, int(bool(flip)),
-                                                 mean, std, ctypes.c_void_p(out.data_ptr()), 16, stream),
-          "ssa_image_u8_crop_flip_normalize")
+    if jitter is not None:
+        out = _jitter_normalize(img_u8, jitter, (x0, y0, cw, ch), flip, mean_std)
+    else:
+        mean = (ctypes.c_float * 3)(*mean_std[0])
+        std = (ctypes.c_float * 3)(*mean_std[1])
+        from ..hip_backend import ACT_DTYPE
+        out = torch.empty((1, ch, cw, 16), dtype=ACT_DTYPE, device=img_u8.device)
+        check(lib().ssa_image_u8_crop_flip_normalize(ctypes.c_void_p(img_u8.data_ptr()), H, W, x0, y0, cw, ch,
+                                                     int(bool(flip)), mean, std, ctypes.c_void_p(out.data_ptr()), 16,
+                                                     stream), "ssa_image_u8_crop_flip_normalize")
     gts = None
     if labels_u8 is not None:
         assert labels_u8.dtype == torch.uint8 and labels_u8.is_cuda and tuple(labels_u8.shape) == (H, W)
@@ -155,6 +161,160 @@ def resize_image_bicubic(img_u8, size):
                                     stream), "ssa_resample_u8")
         cur = out
     return cur
+
+
+# ---------------------------------------------------------------------------------------------
+# ColorJitter on the device (transforms/transforms.py:192-362; datasets/__init__.py:94-99 builds
+# ColorJitter(0.25, 0.25, 0.25, 0.25) under the default --color_aug): ImageEnhance.Brightness / Contrast / Color
+# and the HSV round trip of adjust_hue, bit-identical to Pillow (csrc/color_jitter.hip).  The random draws stay on
+# the host and consume np.random exactly as the reference does; what travels to the kernels is the drawn program.
+# ---------------------------------------------------------------------------------------------
+JITTER_OPS = ("brightness", "contrast", "saturation", "hue")      # index = SSA_JITTER_* of include/semseg_hip.h
+
+
+def hue_to_byte(hue_factor):
+    """The byte adjust_hue adds to H: the reference writes np.uint8(hue_factor * 255), which under the NumPy 1.x it
+    was written for truncates toward zero and wraps modulo 256 (-63.75 -> 193); NumPy 2 raises OverflowError for a
+    negative factor instead.  This is the NumPy 1.x value."""
+    return int(hue_factor * 255) % 256
+
+
+class JitterParams:
+    """One drawn ColorJitter transform: `order` = the enabled operations in application order (names of
+    JITTER_OPS), the three blend factors, the hue factor and the byte it becomes."""
+    __slots__ = ("order", "brightness", "contrast", "saturation", "hue", "hue_byte")
+
+    def __init__(self, order=(), brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, hue_byte=None):
+        self.order = tuple(order)
+        self.brightness, self.contrast, self.saturation, self.hue = (float(brightness), float(contrast),
+                                                                     float(saturation), float(hue))
+        self.hue_byte = hue_to_byte(self.hue) if hue_byte is None else int(hue_byte)
+        if any(op not in JITTER_OPS for op in self.order) or len(set(self.order)) != len(self.order):
+            raise ValueError("JitterParams: order must hold distinct names of %s, not %r" % (JITTER_OPS, self.order))
+        if not 0 <= self.hue_byte <= 255:
+            raise ValueError("JitterParams: hue_byte must be in 0..255")
+
+    def __repr__(self):
+        return "JitterParams(order=%r, brightness=%r, contrast=%r, saturation=%r, hue=%r, hue_byte=%r)" % (
+            self.order, self.brightness, self.contrast, self.saturation, self.hue, self.hue_byte)
+
+    def program(self):
+        """-> the ssa_jitter_program the kernels take by value."""
+        from .._lib import JitterProgram
+        pg = JitterProgram()
+        pg.n_ops = len(self.order)
+        for k, op in enumerate(self.order):
+            pg.op[k] = JITTER_OPS.index(op)
+        pg.factor[0], pg.factor[1], pg.factor[2] = self.brightness, self.contrast, self.saturation
+        pg.hue_byte = self.hue_byte
+        return pg
+
+
+def _jitter_prepare(img_u8, params, window):
+    """Checks + the luma sum the contrast step needs (no launch without one) -> the launch arguments both apply
+    kernels share.  The mean itself is formed on the device: nothing here waits for the sum."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    if not isinstance(params, JitterParams):
+        raise TypeError("jitter parameters must be a JitterParams (ColorJitter.get_params), not %r" % type(params))
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        raise ValueError("the image must be uint8 [H, W, 3]")
+    img_u8 = img_u8.contiguous()
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    x0, y0, cw, ch = (0, 0, W, H) if window is None else (int(v) for v in window)
+    if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= W and y0 + ch <= H):
+        raise ValueError("window %r is empty or not inside the %d x %d image" % ((x0, y0, cw, ch), W, H))
+    pg = params.program()
+    counter = None
+    if "contrast" in params.order:
+        counter = torch.empty((1,), dtype=torch.int64, device=img_u8.device)
+        check(lib().ssa_jitter_luma_sum(hb._p(img_u8), H, W, x0, y0, cw, ch, ctypes.byref(pg), hb._p(counter), hb._s()),
+              "ssa_jitter_luma_sum")
+    return img_u8, (H, W, x0, y0, cw, ch), pg, counter
+
+
+def color_jitter(img_u8, params, window=None, flip=False):
+    """img_u8: uint8 CUDA [H,W,3]; params: JitterParams; window = (x0, y0, w, h) or None for the whole image; flip:
+    mirror the result.  -> uint8 [h,w,3] = the drawn transform applied to the cropped image, as
+    ColorJitter.get_params(...)(img.crop(...)) followed by FLIP_LEFT_RIGHT gives it (the contrast mean is taken over
+    the window and does not depend on the flip)."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    img_u8, (H, W, x0, y0, cw, ch), pg, counter = _jitter_prepare(img_u8, params, window)
+    out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=img_u8.device)
+    check(lib().ssa_jitter_apply_u8(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), ctypes.byref(pg),
+                                    hb._p(counter), hb._p(out), hb._s()), "ssa_jitter_apply_u8")
+    return out
+
+
+def _jitter_normalize(img_u8, params, window, flip, mean_std=MEAN_STD):
+    """The image half of crop_flip_normalize(..., jitter=params): luma sum + the fused apply / normalise launch."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    img_u8, (H, W, x0, y0, cw, ch), pg, counter = _jitter_prepare(img_u8, params, window)
+    mean = (ctypes.c_float * 3)(*mean_std[0])
+    std = (ctypes.c_float * 3)(*mean_std[1])
+    out = torch.empty((1, ch, cw, 16), dtype=hb.ACT_DTYPE, device=img_u8.device)
+    check(lib().ssa_jitter_crop_flip_normalize(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), ctypes.byref(pg),
+                                               hb._p(counter), mean, std, hb._p(out), 16, hb._s()),
+          "ssa_jitter_crop_flip_normalize")
+    return out
+
+
+def adjust_brightness(img_u8, brightness_factor):
+    """transforms/transforms.py:192-209 (ImageEnhance.Brightness) on a uint8 CUDA [H,W,3] image."""
+    return color_jitter(img_u8, JitterParams(("brightness",), brightness=brightness_factor))
+
+
+def adjust_contrast(img_u8, contrast_factor):
+    """transforms/transforms.py:212-229 (ImageEnhance.Contrast)."""
+    return color_jitter(img_u8, JitterParams(("contrast",), contrast=contrast_factor))
+
+
+def adjust_saturation(img_u8, saturation_factor):
+    """transforms/transforms.py:232-249 (ImageEnhance.Color)."""
+    return color_jitter(img_u8, JitterParams(("saturation",), saturation=saturation_factor))
+
+
+def adjust_hue(img_u8, hue_factor):
+    """transforms/transforms.py:252-294: H of the HSV image shifted by hue_to_byte(hue_factor), modulo 256."""
+    if not (-0.5 <= hue_factor <= 0.5):
+        raise ValueError("hue_factor is not in [-0.5, 0.5].")
+    return color_jitter(img_u8, JitterParams(("hue",), hue=hue_factor))
+
+
+class ColorJitter:
+    """transforms/transforms.py:297-362 for uint8 CUDA [H,W,3] images: the same constructor, the same draws from
+    np.random's global generator in the same order, the drawn transform applied on the device."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
+        self.brightness = brightness
+        self.contrast = contrast
+        self.saturation = saturation
+        self.hue = hue
+
+    @staticmethod
+    def get_params(brightness, contrast, saturation, hue):
+        """One np.random.uniform per enabled operation (brightness, contrast, saturation, hue, in that order), then
+        np.random.shuffle of the list of enabled operations -> JitterParams."""
+        factors, order = {}, []
+        if brightness > 0:
+            factors["brightness"] = np.random.uniform(max(0, 1 - brightness), 1 + brightness)
+            order.append("brightness")
+        if contrast > 0:
+            factors["contrast"] = np.random.uniform(max(0, 1 - contrast), 1 + contrast)
+            order.append("contrast")
+        if saturation > 0:
+            factors["saturation"] = np.random.uniform(max(0, 1 - saturation), 1 + saturation)
+            order.append("saturation")
+        if hue > 0:
+            factors["hue"] = np.random.uniform(-hue, hue)
+            order.append("hue")
+        np.random.shuffle(order)        # a list of n entries: the same n - 1 draws whatever it holds
+        return JitterParams(order, **factors)
+
+    def __call__(self, img_u8):
+        return color_jitter(img_u8, self.get_params(self.brightness, self.contrast, self.saturation, self.hue))
 
 
 class DevicePrefetcher:
