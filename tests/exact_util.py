@@ -119,6 +119,24 @@ def assert_bits_equal(name, got, ref, tile=None):
     raise AssertionError(msg)
 
 
+def assert_within_bound(name, got, ref64, bound):
+    """|got - ref| <= bound at EVERY element, counted as `not (err <= bound)`: a NaN (an output the kernel never wrote, a
+    result poisoned by a read of a NaN guard) or an infinity is a violation, never a pass.  bound: a float64 tensor that
+    broadcasts against ref (a zero bound allows no error at all).  Returns the errors."""
+    g, r = got.detach().double().cpu(), ref64.detach().double().cpu()
+    assert tuple(g.shape) == tuple(r.shape), "%s: shape %s != %s" % (name, tuple(g.shape), tuple(r.shape))
+    err = (g - r).abs()
+    bad = ~(err <= bound)
+    n = int(bad.sum())
+    if n:
+        idx = tuple(int(v) for v in bad.nonzero()[0])
+        b = torch.as_tensor(bound, dtype=torch.float64).expand_as(err)
+        raise AssertionError("%s: %d of %d elements exceed their bound (%d of them not finite); first at %s: got %r ref %r "
+                             "error %.3g bound %.3g" % (name, n, err.numel(), int((~torch.isfinite(g)).sum()), idx, float(g[idx]),
+                                                        float(r[idx]), float(err[idx]), float(b[idx])))
+    return err
+
+
 class Guarded:
     """`view`: the tensor a kernel reads or writes; `buf`: the flat buffer around it; `inside`: which elements of buf
     belong to the view."""

@@ -33,10 +33,21 @@ _EXACT_F16 = ("exact_strip and (need_rounding or mode0[c48u4-fwd or mode1[c48u5-
 _EXACT_BN = "exact_bn and (c8 or c48 or c248 or param_grads or plan_mirror) or bn_eval_backward"
 _EXACT_BN_F16 = "exact_bn and (c48 or param_grads)"
 
+# the exact resampling and pooling tests (csrc/resample.hip, csrc/pool.hip through the C ABI): every case of every route
+# table, the bounded cases, the Python dispatch passes, image resize and both pools -- seconds under emulation (the GPU
+# adds the grid-stride cases of 2 M threads and more, which skip here).  The fp16-storage build runs one case per 16-bit
+# route.
+_EXACT_RESAMPLE = "exact_bilinear or exact_image_resize or exact_pool"
+_EXACT_RESAMPLE_F16 = ("exact_bilinear_fwd and (v8-4x-ld or px-c19-4x-in16 or el-c40-in16 or el-c40-out16 or el-c19-16-ld) "
+                       "or exact_bilinear_bwd[ and (v8-4x-ld or v8-8x-ld or el-c19-16-ld or el-c40-out16 or tile-t8-ld-out16) "
+                       "or exact_bilinear_bwd_separable and (v8-4x-ld or v1-16-8x or v1-f32-2x4-out16) "
+                       "or exact_bilinear_autograd and (v8-slices or px16-tile16) or exact_bilinear_upsample_cat "
+                       "or exact_bilinear_bounded and c48-16-up or exact_image_resize or exact_pool")
+
 # (file, -k expression): each entry a few seconds under emulation
 SELECTION = [
     ("tests/test_kernels_gpu.py", "bce_rmi or scale_fusion or cross_entropy or sigmoid or softmax"),
-    ("tests/test_kernels_gpu.py", "probe or bn_train or bn_eval or bn_deferred or bilinear or maxpool or conv_channel_slice"),
+    ("tests/test_kernels_gpu.py", "probe or bn_train or bn_eval or bn_deferred or (bilinear and not exact_bilinear) or maxpool or conv_channel_slice"),
     ("tests/test_kernels_gpu.py", "test_conv_fwd_bwd and (case1] or case10] or case19] or case32] or case33])"),
     ("tests/test_group_gpu.py", "upsample_cat or cat_slots"),
     # round 5: the fused object attention (19 / 65 / 96 regions, ragged pixel counts, the three-launch form), a grouped
@@ -46,14 +57,16 @@ SELECTION = [
     # epilogue mode, and the small cases of the other conv entry points (the GPU runs the full lists)
     ("tests/test_kernels_gpu.py", _EXACT),
     ("tests/test_kernels_gpu.py", _EXACT_BN),
+    ("tests/test_kernels_gpu.py", _EXACT_RESAMPLE),
 ]
 # how many tests an expression must run: a renamed case id would otherwise silently select fewer
-MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10, _EXACT_BN: 27, _EXACT_BN_F16: 8}
+MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10, _EXACT_BN: 27, _EXACT_BN_F16: 8, _EXACT_RESAMPLE: 115, _EXACT_RESAMPLE_F16: 28}
 
 
 # (file, -k expression, extra environment): the fp16-storage build of the same kernels (its own rounding helpers)
 SELECTION_ENV = [("tests/test_kernels_gpu.py", _EXACT_F16, {"SSA_ACT_DTYPE": "fp16"}),
-                 ("tests/test_kernels_gpu.py", _EXACT_BN_F16, {"SSA_ACT_DTYPE": "fp16"})]
+                 ("tests/test_kernels_gpu.py", _EXACT_BN_F16, {"SSA_ACT_DTYPE": "fp16"}),
+                 ("tests/test_kernels_gpu.py", _EXACT_RESAMPLE_F16, {"SSA_ACT_DTYPE": "fp16"})]
 
 
 def _passed_enough(expr, tail):

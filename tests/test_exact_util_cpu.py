@@ -196,3 +196,35 @@ def test_ulp_err32_counts_fp32_spacings():
     with pytest.raises(AssertionError):
         to_f32(torch.tensor([0.1], dtype=torch.float64))
     assert to_f32(torch.tensor([0.375], dtype=torch.float64)).dtype == torch.float32
+
+
+
+from exact_util import assert_within_bound  # noqa: E402
+
+
+def test_within_bound_counts_nan_and_infinity_as_violations():
+    """The comparator of the bounded tests: outputs start as a NaN pattern, so an element the kernel never wrote -- or one
+    poisoned by a read of an input's NaN guard -- must FAIL, although `nan > bound` is False."""
+    ref = torch.arange(12, dtype=torch.float64).view(3, 4)
+    bound = torch.full((3, 4), 0.5, dtype=torch.float64)
+    got = ref.float() + 0.25
+    assert torch.equal(assert_within_bound("ok", got, ref, bound), torch.full((3, 4), 0.25, dtype=torch.float64))
+    assert_within_bound("at the bound", ref + 0.5, ref, bound)
+    for poison in (float("nan"), float("inf"), -float("inf")):
+        bad = got.clone()
+        bad[1, 2] = poison
+        with pytest.raises(AssertionError, match=r"1 of 12 elements exceed their bound \(1 of them not finite\); first at \(1, 2\)"):
+            assert_within_bound("poisoned", bad, ref, bound)
+    guarded_out = guarded((3, 4), torch.float32, "cpu")                  # as a kernel's output buffer starts out
+    with pytest.raises(AssertionError, match="12 of 12 elements"):
+        assert_within_bound("unwritten", guarded_out.view, ref, bound)
+    over = got.clone()
+    over[2, 3] += 0.5
+    with pytest.raises(AssertionError, match=r"1 of 12 elements exceed their bound \(0 of them not finite\); first at \(2, 3\)"):
+        assert_within_bound("over", over, ref, bound)
+    zero = torch.zeros(3, 4, dtype=torch.float64)                        # a zero bound allows no error at all
+    assert_within_bound("exact", ref, ref, zero)
+    with pytest.raises(AssertionError):
+        assert_within_bound("zero bound", ref + 1e-9, ref, zero)
+    with pytest.raises(AssertionError, match="shape"):
+        assert_within_bound("shape", got[:2], ref, bound)

@@ -2427,3 +2427,499 @@ def test_bn_train_large_mean():
     check_close("bn_dx", nchw(dx.float()), xr.grad, 2e-2, 6e-3)
     check_close("bn_dgamma", dg, gr.grad, 1e-2, 4e-3)
     check_close("bn_dbeta", db, br.grad, 1e-2, 4e-3)
+
+
+# ================================================================ exact resampling and pooling tests
+# csrc/resample.hip and csrc/pool.hip through the C ABI, bit for bit against tests/resample_ref.py at power-of-two resize
+# ratios (the premise is asserted on the reference), per element within resize_bound elsewhere.  Every input sits in a
+# NaN-guarded buffer, every output starts as NaN; the case tables are tests/resample_cases.py.
+import resample_cases as RC  # noqa: E402
+from exact_util import LIMIT, assert_within_bound  # noqa: E402
+from resample_ref import (exact_grad_x, exact_resize, exact_resize_grad, grad_amp, half_ulp_act, is_dyadic, resize_bound,  # noqa: E402
+                          resize_grad_ref64, resize_ref64)
+
+_GRID_CAP = 8192 * 256            # grid_for of csrc/resample.hip: threads in flight before a kernel's grid-stride loop turns
+_TILE_CAP = 16384                 # workgroups of the LDS-tiled backward (4 x 16 input pixels each)
+
+
+def _rs():
+    from semseg_amd._lib import check
+    hb = _hb()
+    return hb, hb.lib(), check
+
+
+def _rs_dt(is16):
+    return ACT_DTYPE if is16 else torch.float32
+
+
+def _rs_want(ref64, is16):
+    return to_act(ref64) if is16 else to_f32(ref64)
+
+
+def _ld4(g):
+    return g.view.stride(2)
+
+
+def _rs_fwd(x, in16, out16, Ho, Wo, pads=(0, 0)):
+    """x [B, Hi, Wi, C] (host) through ssa_bilinear_fwd: (guarded input, guarded output)."""
+    hb, L, check = _rs()
+    Bn, Hi, Wi, C = x.shape
+    xg = guarded_copy(x.to(_rs_dt(in16)), DEV, C + pads[0])
+    yg = guarded((Bn, Ho, Wo, C), _rs_dt(out16), DEV, C + pads[1])
+    check(L.ssa_bilinear_fwd(hb._p(xg.view), 0 if in16 else 1, Bn, Hi, Wi, C, _ld4(xg), hb._p(yg.view), 0 if out16 else 1,
+                             Ho, Wo, _ld4(yg), hb._s()), "ssa_bilinear_fwd")
+    return xg, yg
+
+
+def _rs_bwd(dy, dy16, dx16, Hi, Wi, pads=(0, 0)):
+    hb, L, check = _rs()
+    Bn, Ho, Wo, C = dy.shape
+    dyg = guarded_copy(dy.to(_rs_dt(dy16)), DEV, C + pads[0])
+    dxg = guarded((Bn, Hi, Wi, C), _rs_dt(dx16), DEV, C + pads[1])
+    check(L.ssa_bilinear_bwd(hb._p(dyg.view), 0 if dy16 else 1, Bn, Ho, Wo, C, _ld4(dyg), hb._p(dxg.view), 0 if dx16 else 1,
+                             Hi, Wi, _ld4(dxg), hb._s()), "ssa_bilinear_bwd")
+    return dyg, dxg
+
+
+def _rs_bwd_sep(dy, dy16, dx16, Hi, Wi, pads=(0, 0)):
+    """The separable pair: (guarded dy, guarded fp32 tmp [B, Ho, Wi, C], guarded dx)."""
+    hb, L, check = _rs()
+    Bn, Ho, Wo, C = dy.shape
+    dyg = guarded_copy(dy.to(_rs_dt(dy16)), DEV, C + pads[0])
+    tg = guarded((Bn, Ho, Wi, C), torch.float32, DEV)
+    dxg = guarded((Bn, Hi, Wi, C), _rs_dt(dx16), DEV, C + pads[1])
+    check(L.ssa_bilinear_bwd_x(hb._p(dyg.view), 0 if dy16 else 1, Bn, Ho, Wo, C, _ld4(dyg), hb._p(tg.view), Wi, hb._s()),
+          "ssa_bilinear_bwd_x")
+    check(L.ssa_bilinear_bwd_y(hb._p(tg.view), Bn, Ho, Wi, C, hb._p(dxg.view), 0 if dx16 else 1, Hi, _ld4(dxg), hb._s()),
+          "ssa_bilinear_bwd_y")
+    return dyg, tg, dxg
+
+
+# ---- 3a: exact by route
+@pytest.mark.parametrize("case", RC.FWD_EXACT, ids=[c[0] for c in RC.FWD_EXACT])
+def test_exact_bilinear_fwd(case):
+    """ssa_bilinear_fwd bit for bit on its three kernels (8 channels per thread, per pixel, per element in the four dtype
+    pairs), dense and with leading dimensions that differ from C."""
+    name, C, Hi, Wi, Ho, Wo, in16, out16, pads = case
+    x = RC.fwd_operand(case)
+    ref = exact_resize(name, x, Ho, Wo)
+    xg, yg = _rs_fwd(x, in16, out16, Ho, Wo, pads)
+    torch.cuda.synchronize()
+    assert_bits_equal("bilinear_fwd %s" % name, yg.view.cpu(), _rs_want(ref, out16))
+    assert_guard_intact("bilinear_fwd %s" % name, xg, yg)
+
+
+@pytest.mark.parametrize("case", RC.BWD_EXACT, ids=[c[0] for c in RC.BWD_EXACT])
+def test_exact_bilinear_bwd(case):
+    """ssa_bilinear_bwd bit for bit: the vectorised gather (hoisted and recomputed weights), the per-element gather and
+    the LDS-tiled kernel (TAPS 4 and 8; 8 and 32 channels; ragged, full and one-pixel tiles)."""
+    name, C, Hi, Wi, Ho, Wo, dy16, dx16, pads = case
+    dy = RC.bwd_operand(case)
+    ref = exact_resize_grad(name, dy, Hi, Wi)
+    dyg, dxg = _rs_bwd(dy, dy16, dx16, Hi, Wi, pads)
+    torch.cuda.synchronize()
+    assert_bits_equal("bilinear_bwd %s" % name, dxg.view.cpu(), _rs_want(ref, dx16))
+    assert_guard_intact("bilinear_bwd %s" % name, dyg, dxg)
+
+
+@pytest.mark.parametrize("case", RC.SEP_EXACT, ids=[c[0] for c in RC.SEP_EXACT])
+def test_exact_bilinear_bwd_separable(case):
+    """ssa_bilinear_bwd_x then _y: the fp32 intermediate AND the result bit for bit (a failure is located to a pass), and
+    the one-launch form ssa_bilinear_bwd of the same problem equal to the same reference."""
+    name, C, Hi, Wi, Ho, Wo, dy16, dx16, pads = case
+    dy = RC.bwd_operand(case)
+    ref = exact_resize_grad(name, dy, Hi, Wi)
+    tref = exact_grad_x(name, dy, Wi)
+    dyg, tg, dxg = _rs_bwd_sep(dy, dy16, dx16, Hi, Wi, pads)
+    torch.cuda.synchronize()
+    assert_bits_equal("bilinear_bwd_x %s" % name, tg.view.cpu(), to_f32(tref))
+    assert_bits_equal("bilinear_bwd_y %s" % name, dxg.view.cpu(), _rs_want(ref, dx16))
+    assert_guard_intact("bilinear_bwd_x/_y %s" % name, dyg, tg, dxg)
+    if dy16 == dx16 or not dy16:                          # (ssa_bilinear_bwd has no 16-bit -> fp32 form)
+        dyg2, dxg2 = _rs_bwd(dy, dy16, dx16, Hi, Wi, pads)
+        torch.cuda.synchronize()
+        assert_bits_equal("bilinear_bwd (one launch) %s" % name, dxg2.view.cpu(), _rs_want(ref, dx16))
+        assert_guard_intact("bilinear_bwd (one launch) %s" % name, dyg2, dxg2)
+
+
+# the Python dispatch: (id, C, Hi, Wi, Ho, Wo, x 16-bit, output fp32, layout)
+_RS_AUTOGRAD = [
+    ("v8-separable", 48, 5, 7, 20, 28, True, False, "dense"),          # separable() true: bwd_x / bwd_y
+    ("v8-separable-2x4", 48, 5, 7, 10, 28, True, False, "dense"),
+    ("v8-gather-down", 48, 12, 20, 6, 10, True, False, "dense"),       # separable() false: the vectorised gather
+    ("v8-gather-2x-by-1x", 48, 5, 7, 10, 7, True, False, "dense"),     # one axis below 2x: separable() false
+    ("v8-slices", 48, 5, 7, 10, 14, True, False, "slices"),            # x a channel slice; dy a slice with ld % 8 != 0: re-packed
+    ("px-tile", 19, 9, 21, 36, 84, False, True, "dense"),
+    ("px16-tile16", 19, 9, 21, 36, 84, True, True, "dense"),
+    ("px-tile-slices", 19, 9, 21, 18, 42, False, True, "slices"),
+    ("el-f32", 40, 9, 21, 18, 42, False, True, "dense"),
+    ("el-16", 19, 6, 10, 12, 20, True, False, "slices"),
+]
+
+
+@pytest.mark.parametrize("case", _RS_AUTOGRAD, ids=[c[0] for c in _RS_AUTOGRAD])
+def test_exact_bilinear_autograd(case):
+    """One pass per route through BilinearFn: _pixels on channel slices, the separable() predicate, the re-pack of a
+    16-bit gradient whose leading dimension is no multiple of 8."""
+    hb = _hb()
+    name, C, Hi, Wi, Ho, Wo, x16, out_f32, layout = case
+    x, dy = RC.fwd_operand(case), RC.bwd_operand(case)
+    ref, gref = exact_resize(name, x, Ho, Wo), exact_resize_grad(name, dy, Hi, Wi)
+    out16 = x16 and not out_f32
+    if layout == "dense":
+        xd = x.to(_rs_dt(x16)).to(DEV).requires_grad_(True)
+        dyd = dy.to(_rs_dt(out16)).to(DEV)
+    else:
+        xg = guarded_copy(x.to(_rs_dt(x16)), DEV, C + 8)
+        dyg = guarded_copy(dy.to(_rs_dt(out16)), DEV, C + 4)
+        xd, dyd = xg.view.detach().requires_grad_(True), dyg.view
+    yd = hb.BilinearFn.apply(xd, Ho, Wo, out_f32)
+    yd.backward(dyd)
+    torch.cuda.synchronize()
+    assert_bits_equal("BilinearFn %s forward" % name, yd.detach().cpu(), _rs_want(ref, out16))
+    assert_bits_equal("BilinearFn %s backward" % name, xd.grad.cpu(), _rs_want(gref, x16))
+    if layout != "dense":
+        assert_guard_intact("BilinearFn %s" % name, xg, dyg)
+
+
+def test_exact_bilinear_upsample_cat():
+    """UpsampleCatGroupFn: an identity copy, a 2x and a 4x resize written into channel slices of one buffer (ldy = 80),
+    and the backward reading its slices of the gradient in place (lddy = 80)."""
+    hb = _hb()
+    shapes = [(16, 12, 20), (48, 6, 10), (16, 3, 5)]
+    Ho, Wo = 12, 20
+    xs = [ints((RC.B, H, W, C), -200, 200, 420 + i) for i, (C, H, W) in enumerate(shapes)]
+    dys = [ints((RC.B, Ho, Wo, C), -grad_amp(Ho, H, Wo, W, 200), grad_amp(Ho, H, Wo, W, 200), 430 + i)
+           for i, (C, H, W) in enumerate(shapes)]
+    want = torch.cat([to_act(exact_resize("cat %d" % i, x, Ho, Wo)) for i, x in enumerate(xs)], 3)
+    gwant = [to_act(exact_resize_grad("cat %d" % i, dy, H, W)) for i, (dy, (C, H, W)) in enumerate(zip(dys, shapes))]
+    assert not_representable(exact_resize_grad("cat 2", dys[2], 3, 5)) > 0
+    xgs = [guarded_copy(x.to(ACT_DTYPE), DEV) for x in xs]
+    leaves = [g.view.detach().requires_grad_(True) for g in xgs]
+    dyg = guarded_copy(torch.cat(dys, 3).to(ACT_DTYPE), DEV)
+    (y,) = hb.UpsampleCatGroupFn.apply((3,), *leaves)
+    y.backward(dyg.view)
+    torch.cuda.synchronize()
+    assert_bits_equal("UpsampleCat forward", y.detach().cpu(), want)
+    for i, leaf in enumerate(leaves):
+        assert_bits_equal("UpsampleCat backward %d" % i, leaf.grad.cpu(), gwant[i])
+    assert_guard_intact("UpsampleCat", dyg, *xgs)
+
+
+# ---- 3b: bounded by route
+def _rs_bounded(tag, got, ref, bound, idx, variants=None):
+    """Every element within its bound.  Prints the worst error / bound with the index term's share of that bound, and the
+    worst error in units of the bound WITHOUT the index term.  variants (fp32 outputs; a diagnosis, not asserted): the
+    references whose source index is rounded once, as a contracted multiply-add would, on either axis, each with its own
+    arithmetic term -- the last figure is then taken against the nearest of the four per element: near or below 1 says the index term is what a
+    contraction needs, and which ones fit says whether the device contracts."""
+    def over(e, b):                                         # e / b per element; a zero bound allows no error at all
+        return torch.where(b > 0, e / b.clamp_min(1e-300), torch.where(e > 0, torch.full_like(e, float("inf")), torch.zeros_like(e)))
+    err = (got.detach().double().cpu() - ref).abs()
+    ratio = over(err, bound)
+    k = int(ratio.flatten().argmax())
+    share = float(idx.flatten()[k] / bound.flatten()[k]) if float(bound.flatten()[k]) > 0 else 0.0
+    rest = bound - idx
+    line = "[resize_bound] %-36s worst error / bound = %.3g (index term %.0f%% of that bound); error / (bound - index term) = %.3g" % (
+        tag, float(ratio.flatten()[k]), 100 * share, float(over(err, rest).max()))
+    if variants:
+        each = [over((got.detach().double().cpu() - v).abs(), r) for v, r in [(ref, rest)] + variants]
+        line += "; against the nearest of the single-rounding variants %.3g (each alone: %s)" % (
+            float(torch.stack(each).min(0).values.max()), " ".join("%.3g" % float(e.max()) for e in each))
+    print(line)
+    assert_within_bound("resize_bound " + tag, got, ref, bound)           # NaN-safe: an unwritten output is a violation
+
+
+_FMA_VARIANTS = ((True, False), (False, True), (True, True))
+
+
+@pytest.mark.parametrize("case", RC.BOUNDED, ids=[c[0] for c in RC.BOUNDED])
+def test_exact_bilinear_bounded(case):
+    """Ratios that are not dyadic: every element of forward and backward within resize_bound of the float64 reference,
+    dense and sliced; the 16-bit upsampling cases through the separable pair as well."""
+    name, C, Hi, Wi, Ho, Wo, is16 = case
+    x, dy = RC.bounded_operands(case)
+    ref, _ = resize_ref64(x, Ho, Wo)
+    gref, _ = resize_grad_ref64(dy, Hi, Wi)
+    bf, idf = resize_bound(x, Ho, Wo, Hi, Wi, False, is16, ref)
+    bb, idb = resize_bound(dy, Ho, Wo, Hi, Wi, True, is16, gref)
+    def arith(v, backward, fma):
+        b, i = resize_bound(v, Ho, Wo, Hi, Wi, backward, False, None, fma)
+        return b - i
+    vf = None if is16 else [(resize_ref64(x, Ho, Wo, v)[0], arith(x, False, v)) for v in _FMA_VARIANTS]
+    vb = None if is16 else [(resize_grad_ref64(dy, Hi, Wi, v)[0], arith(dy, True, v)) for v in _FMA_VARIANTS]
+    for pads in ((0, 0), (16, 8) if is16 else (5, 3)):
+        tag = "%s %s" % (name, "dense" if pads == (0, 0) else "sliced")
+        xg, yg = _rs_fwd(x, is16, is16, Ho, Wo, pads)
+        dyg, dxg = _rs_bwd(dy, is16, is16, Hi, Wi, pads)
+        torch.cuda.synchronize()
+        _rs_bounded("fwd " + tag, yg.view, ref, bf, idf, vf)
+        _rs_bounded("bwd " + tag, dxg.view, gref, bb, idb, vb)
+        assert_guard_intact("bilinear bounded " + tag, xg, yg, dyg, dxg)
+        if is16 and Ho >= 2 * Hi and Wo >= 2 * Wi:
+            dyg, tg, dxg = _rs_bwd_sep(dy, True, True, Hi, Wi, pads)
+            torch.cuda.synchronize()
+            _rs_bounded("bwd separable " + tag, dxg.view, gref, bb, idb)
+            assert_guard_intact("bilinear bounded separable " + tag, dyg, tg, dxg)
+
+
+# ---- 3c: the grid-stride loops (GPU only)
+def _dev_ints(shape, amp, seed):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return torch.randint(-amp, amp + 1, shape, generator=g, device=DEV, dtype=torch.int32)
+
+
+def _dev_resize64(x, Ho, Wo):
+    """torch's own float64 interpolate on the device, NHWC in and out (any correct float64 bilinear is THE reference at a
+    dyadic ratio); with it the same of |x| for the premise."""
+    F = torch.nn.functional
+    xd = x.permute(0, 3, 1, 2).double()
+    y = F.interpolate(xd, size=(Ho, Wo), mode="bilinear", align_corners=False)
+    mag = float(F.interpolate(xd.abs(), size=(Ho, Wo), mode="bilinear", align_corners=False).max())
+    return y.permute(0, 2, 3, 1).contiguous(), mag
+
+
+def _dev_grad64(dy, Hi, Wi):
+    """The float64 gradient of that interpolate (ATen's own backward), image by image to bound the memory."""
+    Bn, Ho, Wo, C = dy.shape
+    out, mag = [], 0.0
+    for b in range(Bn):
+        g = dy[b:b + 1].permute(0, 3, 1, 2).double().contiguous()
+        out.append(torch.ops.aten.upsample_bilinear2d_backward(g, [Ho, Wo], [1, C, Hi, Wi], False, None, None).permute(0, 2, 3, 1))
+        mag = max(mag, float(torch.ops.aten.upsample_bilinear2d_backward(g.abs(), [Ho, Wo], [1, C, Hi, Wi], False, None, None).max()))
+        del g
+    return torch.cat(out).contiguous(), mag
+
+
+def _dev_want(tag, ref64, mag, is16, sizes):
+    """The premise of the exact tests, asserted on the device reference; the reference in the output's format."""
+    for n_out, n_in in sizes:
+        assert is_dyadic(n_out, n_in), (tag, n_out, n_in)
+    assert mag * 65536.0 < LIMIT, "%s: exactness premise violated: the magnitude product reaches %g" % (tag, mag)
+    f = ref64.float()
+    assert torch.equal(f.double(), ref64), "%s: the reference is not exact in fp32" % tag
+    return f.to(ACT_DTYPE) if is16 else f
+
+
+def _dev_bits_equal(tag, got, want):
+    """Bitwise comparison where the tensors live; on a mismatch the first differing image row goes through
+    assert_bits_equal for its report."""
+    it = torch.int16 if got.element_size() == 2 else torch.int32
+    assert got.dtype == want.dtype and got.shape == want.shape
+    bad = got.contiguous().view(it) != want.contiguous().view(it)
+    n = int(bad.sum())
+    if n:
+        b, h = (int(v) for v in bad.nonzero()[0][:2])
+        assert_bits_equal("%s: %d elements differ in all, first in image %d row %d" % (tag, n, b, h),
+                          got[b, h].cpu(), want[b, h].cpu())
+
+
+def _dev_operand(shape, amp, seed, is16, ld):
+    """Integer operand generated on the device inside a guarded buffer; asserted representable."""
+    v = _dev_ints(shape, amp, seed)
+    g = guarded(shape, _rs_dt(is16), DEV, ld)
+    g.view.copy_(v)
+    assert torch.equal(g.view.to(torch.int32), v), "operand not representable"
+    return g
+
+
+_GS_KERNELS = ["fwd-v8", "fwd-px", "fwd-el", "bwd-v8-and-separable", "bwd-el", "bwd-tile"]
+
+
+@pytest.mark.skipif(bool(os.environ.get("SSA_EMU")), reason="2 M threads and more: GPU only")
+@pytest.mark.parametrize("kernel", _GS_KERNELS)
+def test_exact_bilinear_grid_stride(kernel):
+    """One exact 2x (0.5x) case per kernel just past its grid cap -- 8192 x 256 threads, 16384 tiles for the tiled
+    backward -- at sizes that are no multiple of 256 or of the tile, so that the grid-stride loop turns and its last
+    turn is ragged.  Reference and comparison on the device."""
+    hb, L, check = _rs()
+    Bn, C = RC.B, 8
+    if kernel.startswith("fwd"):
+        Hi = Wi = 515
+        Ho = Wo = 1030
+        in16, out16, pads = {"fwd-v8": (True, True, (8, 24)), "fwd-px": (False, False, (5, 0)), "fwd-el": (False, True, (5, 3))}[kernel]
+        threads = Bn * Ho * Wo * (C if kernel == "fwd-el" else 1)
+        assert threads > _GRID_CAP and threads % 256
+        xg = _dev_operand((Bn, Hi, Wi, C), 200, 440, in16, C + pads[0])
+        yg = guarded((Bn, Ho, Wo, C), _rs_dt(out16), DEV, C + pads[1])
+        check(L.ssa_bilinear_fwd(hb._p(xg.view), 0 if in16 else 1, Bn, Hi, Wi, C, _ld4(xg), hb._p(yg.view), 0 if out16 else 1,
+                                 Ho, Wo, _ld4(yg), hb._s()), "ssa_bilinear_fwd")
+        ref, mag = _dev_resize64(xg.view, Ho, Wo)
+        want = _dev_want(kernel, ref, mag, out16, [(Ho, Hi), (Wo, Wi)])
+        if out16:
+            assert int((want.double() != ref).sum()) > 0, "no output needs rounding"
+        torch.cuda.synchronize()
+        _dev_bits_equal("grid stride " + kernel, yg.view, want)
+        assert_guard_intact("grid stride " + kernel, xg, yg)
+        return
+    if kernel == "bwd-v8-and-separable":
+        Hi = Wi = 1030
+        Ho = Wo = 2060
+        assert Bn * Hi * Wi > _GRID_CAP and Bn * Ho * Wi > _GRID_CAP and (Bn * Hi * Wi) % 256        # pass Y / the gather; pass X
+        dyg = _dev_operand((Bn, Ho, Wo, C), grad_amp(Ho, Hi, Wo, Wi), 441, True, C + 8)
+        tg = guarded((Bn, Ho, Wi, C), torch.float32, DEV)
+        dxg, dxg2 = (guarded((Bn, Hi, Wi, C), ACT_DTYPE, DEV, C + 8) for _ in range(2))
+        check(L.ssa_bilinear_bwd_x(hb._p(dyg.view), 0, Bn, Ho, Wo, C, _ld4(dyg), hb._p(tg.view), Wi, hb._s()), "ssa_bilinear_bwd_x")
+        check(L.ssa_bilinear_bwd_y(hb._p(tg.view), Bn, Ho, Wi, C, hb._p(dxg.view), 0, Hi, _ld4(dxg), hb._s()), "ssa_bilinear_bwd_y")
+        check(L.ssa_bilinear_bwd(hb._p(dyg.view), 0, Bn, Ho, Wo, C, _ld4(dyg), hb._p(dxg2.view), 0, Hi, Wi, _ld4(dxg2), hb._s()),
+              "ssa_bilinear_bwd")
+        tref, tmag = _dev_grad64(dyg.view, Ho, Wi)                                                   # the X pass alone: a 1x resize in y
+        twant = _dev_want(kernel + " pass X", tref, tmag, False, [(Wo, Wi)])
+        del tref
+        ref, mag = _dev_grad64(dyg.view, Hi, Wi)
+        want = _dev_want(kernel, ref, mag, True, [(Ho, Hi), (Wo, Wi)])
+        assert int((want.double() != ref).sum()) > 0, "no output needs rounding"
+        torch.cuda.synchronize()
+        _dev_bits_equal("grid stride bwd_x", tg.view, twant)
+        _dev_bits_equal("grid stride bwd_y", dxg.view, want)
+        _dev_bits_equal("grid stride vectorised gather", dxg2.view, want)
+        assert_guard_intact("grid stride " + kernel, dyg, tg, dxg, dxg2)
+        return
+    if kernel == "bwd-el":                                   # 0.5x: a downsampling gradient never takes the tiled route
+        Hi = Wi = 1030
+        Ho = Wo = 515
+        assert Bn * Hi * Wi * C > _GRID_CAP
+    else:                                                    # 2 * 183 * 46 tiles of 4 x 16; 730 = 182 * 4 + 2 = 45 * 16 + 10
+        Hi = Wi = 730
+        Ho = Wo = 1460
+        assert Bn * (-(-Hi // 4)) * (-(-Wi // 16)) > _TILE_CAP and Hi % 4 and Wi % 16
+    dyg = _dev_operand((Bn, Ho, Wo, C), grad_amp(Ho, Hi, Wo, Wi, 200), 442, False, C + 5)
+    dxg = guarded((Bn, Hi, Wi, C), torch.float32, DEV, C + 3)
+    check(L.ssa_bilinear_bwd(hb._p(dyg.view), 1, Bn, Ho, Wo, C, _ld4(dyg), hb._p(dxg.view), 1, Hi, Wi, _ld4(dxg), hb._s()),
+          "ssa_bilinear_bwd")
+    ref, mag = _dev_grad64(dyg.view, Hi, Wi)
+    want = _dev_want(kernel, ref, mag, False, [(Ho, Hi), (Wo, Wi)])
+    torch.cuda.synchronize()
+    _dev_bits_equal("grid stride " + kernel, dxg.view, want)
+    assert_guard_intact("grid stride " + kernel, dyg, dxg)
+
+
+# ---- 3d: the neighbours in the same family
+def _image_resize(x, Ho, Wo, cpad=16):
+    hb, L, check = _rs()
+    Bn, C, Hi, Wi = x.shape
+    xg = guarded_copy(x, DEV)
+    yg = guarded((Bn, Ho, Wo, cpad), ACT_DTYPE, DEV)
+    check(L.ssa_image_resize_to_nhwc_bf16(hb._p(xg.view), Bn, C, Hi, Wi, hb._p(yg.view), Ho, Wo, cpad, hb._s()),
+          "ssa_image_resize_to_nhwc_bf16")
+    return xg, yg
+
+
+@pytest.mark.parametrize("Hi,Wi,Ho,Wo", [(12, 20, 6, 10), (9, 21, 9, 21), (9, 21, 18, 42), (9, 21, 36, 42)],
+                         ids=["half", "copy", "2x", "4x-by-2x"])
+def test_exact_image_resize(Hi, Wi, Ho, Wo):
+    """ssa_image_resize_to_nhwc_bf16 of an integer image: the three channels bit for bit, the thirteen padding channels
+    exactly zero, nothing written around the output.  The image is fp32, so its integers go to 250: halves and quarters
+    of them need rounding in bf16 (in fp16 at 2x and 4x)."""
+    x = ints((RC.B, 3, Hi, Wi), -250, 250, 450)
+    ref = exact_resize("image", nhwc(x), Ho, Wo)
+    want = torch.zeros((RC.B, Ho, Wo, 16), dtype=ACT_DTYPE)
+    want[..., :3] = to_act(ref)
+    xg, yg = _image_resize(x, Ho, Wo)
+    torch.cuda.synchronize()
+    assert_bits_equal("image_resize", yg.view.cpu(), want)
+    assert_guard_intact("image_resize", xg, yg)
+    through = _hb().image_to_nhwc(xg.view, None if (Hi, Wi) == (Ho, Wo) else (Ho, Wo))
+    torch.cuda.synchronize()
+    assert_bits_equal("image_to_nhwc", through.cpu(), want)
+
+
+def test_exact_image_resize_bounded():
+    """A size that is not dyadic: every element within resize_bound, the padding exactly zero."""
+    Hi, Wi, Ho, Wo = 13, 17, 40, 27
+    x = ints((RC.B, 3, Hi, Wi), -64, 64, 451)
+    ref, _ = resize_ref64(nhwc(x), Ho, Wo)
+    bound, idx = resize_bound(nhwc(x), Ho, Wo, Hi, Wi, False, True, ref)
+    xg, yg = _image_resize(x, Ho, Wo)
+    torch.cuda.synchronize()
+    _rs_bounded("image_resize 13x17 -> 40x27", yg.view[..., :3], ref, bound, idx)
+    assert_bits_equal("image_resize padding", yg.view[..., 3:].cpu(), torch.zeros((RC.B, Ho, Wo, 13), dtype=ACT_DTYPE))
+    assert_guard_intact("image_resize bounded", xg, yg)
+
+
+@pytest.mark.parametrize("Bn,C,H,W", [(1, 8, 5, 7), (1, 64, 33, 47), (2, 8, 5, 7)])
+def test_exact_pool_max(Bn, C, H, W):
+    """Max-pool 3x3 / 2 on post-ReLU integers (half of them zero, the rest in 1..3: ties in nearly every window): values and
+    the gradient bit for bit against PyTorch's first-maximum rule in float64 -- an integer dy makes every dx a sum of at
+    most four integers -- with the input a channel slice (ldx = C + 8)."""
+    hb, L, check = _rs()
+    F = torch.nn.functional
+    x = torch.relu(ints((Bn, H, W, C), -3, 3, 460))
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    dy = ints((Bn, Ho, Wo, C), -16, 16, 461)
+    assert_integers("maxpool", x, dy)
+    xr = nchw(x).double().requires_grad_(True)
+    yr = F.max_pool2d(xr, 3, 2, 1)
+    yr.backward(nchw(dy).double())
+    assert float((x == 0).float().mean()) > 0.4
+    xg = guarded_copy(x.to(ACT_DTYPE), DEV, C + 8)
+    yg = guarded((Bn, Ho, Wo, C), ACT_DTYPE, DEV)
+    ig = guarded((Bn, Ho, Wo, C), torch.uint8, DEV)
+    dyg = guarded_copy(dy.to(ACT_DTYPE), DEV)
+    dxg = guarded((Bn, H, W, C), ACT_DTYPE, DEV)
+    check(L.ssa_maxpool3x3s2_fwd(hb._p(xg.view), _ld4(xg), Bn, H, W, C, hb._p(yg.view), hb._p(ig.view), Ho, Wo, hb._s()),
+          "ssa_maxpool3x3s2_fwd")
+    check(L.ssa_maxpool3x3s2_bwd(hb._p(dyg.view), hb._p(ig.view), Bn, Ho, Wo, C, hb._p(dxg.view), H, W, hb._s()),
+          "ssa_maxpool3x3s2_bwd")
+    torch.cuda.synchronize()
+    assert_bits_equal("maxpool y", yg.view.cpu(), to_act(nhwc(yr.detach())))
+    assert int(ig.view.max()) <= 8
+    assert_bits_equal("maxpool dx", dxg.view.cpu(), to_act(nhwc(xr.grad)))
+    assert_guard_intact("maxpool", xg, yg, ig, dyg, dxg)
+    # the same through autograd
+    xd = xg.view.detach().requires_grad_(True)
+    yd = hb.MaxPool3x3s2Fn.apply(xd)
+    yd.backward(dyg.view)
+    torch.cuda.synchronize()
+    assert_bits_equal("MaxPool3x3s2Fn dx", xd.grad.cpu(), to_act(nhwc(xr.grad)))
+
+
+def _gap(x, dout, pads):
+    hb, L, check = _rs()
+    Bn, H, W, C = x.shape
+    xg = guarded_copy(x.to(ACT_DTYPE), DEV, C + pads)
+    og = guarded((Bn, C), ACT_DTYPE, DEV)
+    dg = guarded_copy(dout.to(ACT_DTYPE), DEV)
+    dxg = guarded((Bn, H, W, C), ACT_DTYPE, DEV)
+    check(L.ssa_global_avg_pool_fwd(hb._p(xg.view), _ld4(xg), Bn, H * W, C, hb._p(og.view), hb._s()), "ssa_global_avg_pool_fwd")
+    check(L.ssa_global_avg_pool_bwd(hb._p(dg.view), Bn, H * W, C, hb._p(dxg.view), hb._s()), "ssa_global_avg_pool_bwd")
+    torch.cuda.synchronize()
+    return xg, og, dg, dxg
+
+
+@pytest.mark.parametrize("H,W", [(8, 16), (32, 64)], ids=["hw128", "hw2048"])
+def test_exact_pool_gap(H, W):
+    """Global average pool with HW a power of two: the fp32 sum of integers is exact (sum |x| < 2^24) and so is the
+    division, the mean is rounded once; the backward dout / HW is exact.  HW = 2048: a thread sums eight pixels.  The
+    input is a channel slice (ldx = C + 8)."""
+    Bn, C = RC.B, 24
+    x, dout = ints((Bn, H, W, C), -200, 200, 470), ints((Bn, C), -200, 200, 471)
+    assert_integers("gap", x, dout)
+    assert_premise("gap", x.double().abs().sum((1, 2)))
+    ref = x.double().mean((1, 2))
+    gref = (dout.double() / (H * W))[:, None, None, :].expand(Bn, H, W, C)
+    assert not_representable(ref) > 0
+    xg, og, dg, dxg = _gap(x, dout, 8)
+    assert_bits_equal("gap fwd", og.view.cpu(), to_act(ref))
+    assert_bits_equal("gap bwd", dxg.view.cpu(), to_act(gref.contiguous()))
+    assert_guard_intact("gap", xg, og, dg, dxg)
+
+
+def test_exact_pool_gap_bounded():
+    """HW = 12 * 16, no power of two: against float64 within (HW + 2) 2^-24 mean|x| -- HW - 1 additions in any order, the
+    division -- plus the rounding of the output; the backward within 2 * 2^-24 |dout| / HW (the reciprocal, the
+    product) plus the same."""
+    Bn, C, H, W = RC.B, 24, 12, 16
+    hw = H * W
+    x, dout = ints((Bn, H, W, C), -64, 64, 472), ints((Bn, C), -64, 64, 473)
+    ref = x.double().mean((1, 2))
+    gref = (dout.double() / hw)[:, None, None, :].expand(Bn, H, W, C).contiguous()
+    xg, og, dg, dxg = _gap(x, dout, 8)
+    b = (hw + 2) * 2.0 ** -24 * x.double().abs().mean((1, 2))
+    b = b + half_ulp_act(ref.abs() + b)
+    gb = 2 * 2.0 ** -24 * gref.abs()
+    gb = gb + half_ulp_act(gref.abs() + gb)
+    zero = torch.zeros(())
+    _rs_bounded("gap fwd HW=192", og.view, ref, b, zero.expand_as(b))
+    _rs_bounded("gap bwd HW=192", dxg.view, gref, gb, zero.expand_as(gb))
+    assert_guard_intact("gap bounded", xg, og, dg, dxg)
