@@ -685,6 +685,37 @@ int ssa_jitter_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, i
                                    const unsigned long long* counter, const float* mean3, const float* std3,
                                    void* out_nhwc_bf16, int cpad, void* stream);
 
+/* RandomGaussianBlur on the device (transforms/transforms.py:154-162; datasets/__init__.py:102 appends it under
+ * --gblur): skimage.filters.gaussian(img, sigma, multichannel=True) * 255 truncated to uint8, i.e. the bytes as
+ * float64 (x * (1 / 255): the 256-entry table lut256), scipy.ndimage.gaussian_filter(., [sigma, sigma, 0],
+ * mode='nearest', truncate=4.0), bit for bit (csrc/gblur.hip states the arithmetic).  The taps are a HOST struct,
+ * passed to the kernel by value: radius = int(4 sigma + 0.5) in 1..5 -- the reference's whole interval of sigma,
+ * [0.15, 1.3) --, w[j] the normalised weight at distance j (w[j] for j > radius is not read, but must be finite). */
+typedef struct ssa_gblur_taps {
+  int radius;   /* 1..5 */
+  double w[6];  /* w[0] centre ... w[radius] */
+} ssa_gblur_taps;
+
+/* transforms/transforms.py:154-162, datasets/__init__.py:102 -- the blur of the window (x0, y0, cw, ch) of img_hwc
+ * (uint8 [H][W][3] on the device), optionally mirrored: out_hwc uint8 [ch][cw][3].  Indices beyond the WINDOW's
+ * edges are clamped to the window, not to the source image: the reference blurs the cropped image.  program: NULL, or
+ * the ColorJitter program to run on every pixel before the blur (the reference's order); a program with a contrast
+ * step reads the mean from `counter` as ssa_jitter_luma_sum left it (same window, same program, same stream; no
+ * host synchronisation).  lut256: 256 doubles on the DEVICE, lut256[b] = the float64 the reference makes of byte b. */
+int ssa_gblur_u8(const unsigned char* img_hwc, int H, int W, int x0, int y0, int cw, int ch, int flip,
+                 const ssa_jitter_program* program, const unsigned long long* counter,
+                 const ssa_gblur_taps* taps, const double* lut256, unsigned char* out_hwc, void* stream);
+/* transforms/transforms.py:154-162, datasets/__init__.py:102 followed by ToTensor + Normalize
+ * (datasets/__init__.py:104-107): ssa_gblur_u8 fused with the arithmetic and the NHWC [ch][cw][cpad] store of
+ * ssa_image_u8_crop_flip_normalize, in the build's 16-bit element type; cpad must be 16.  Bit-identical to the two in
+ * sequence.  Both return -1 before touching the device on a bad window, a radius outside 1..5, a null pointer, a cpad
+ * other than 16, an invalid program, or a program with a contrast step and no counter.                      */
+int ssa_gblur_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, int x0, int y0, int cw, int ch,
+                                  int flip, const ssa_jitter_program* program,
+                                  const unsigned long long* counter, const ssa_gblur_taps* taps,
+                                  const double* lut256, const float* mean3, const float* std3, void* out_nhwc,
+                                  int cpad, void* stream);
+
 /* Evaluation tail on the device (utils/trnval_utils.py:173-196 + utils/misc.py:50-67
  * fast_hist): pred[p] = first argmax_c logits[p,c] (uint8, optional) and
  * hist[gt*C + pred] += 1 for 0 <= gt < C (int64 [C*C], ACCUMULATED: clear it once per

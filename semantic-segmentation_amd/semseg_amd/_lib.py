@@ -30,7 +30,7 @@ def source_sha():
     import glob
     import hashlib
     # (the same files in the same order as SRCS + HDRS of csrc/Makefile)
-    files = sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + [os.path.join(CSRC, h) for h in ("common.h", "conv_epilogue.h", "group.h")] + [
+    files = sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + [os.path.join(CSRC, h) for h in ("common.h", "conv_epilogue.h", "group.h", "jitter_device.h")] + [
         os.path.normpath(os.path.join(_HERE, "..", "..", "include", "semseg_hip.h"))]
     if not files or not all(os.path.exists(f) for f in files):
         return None
@@ -76,6 +76,11 @@ class ConvDesc(ctypes.Structure):
 class JitterProgram(ctypes.Structure):
     """Mirror of ssa_jitter_program (36 bytes)."""
     _fields_ = [("n_ops", c_int), ("op", c_int * 4), ("factor", c_float * 3), ("hue_byte", c_int)]
+
+
+class GblurTaps(ctypes.Structure):
+    """Mirror of ssa_gblur_taps (56 bytes)."""
+    _fields_ = [("radius", c_int), ("w", c_double * 6)]
 
 
 _P = c_void_p
@@ -197,6 +202,10 @@ _SIGS = {
                             c_int),
     "ssa_jitter_crop_flip_normalize": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P,
                                         _P, _P, _P, c_int, _P], c_int),
+    "ssa_gblur_u8": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P, POINTER(GblurTaps),
+                      _P, _P, _P], c_int),
+    "ssa_gblur_crop_flip_normalize": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P,
+                                       POINTER(GblurTaps), _P, _P, _P, _P, c_int, _P], c_int),
     "ssa_confusion_matrix": ([_P, c_int, _P, c_long, c_int, _P, _P, _P], c_int),
     "ssa_eval_tail": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P,
                        _P, _P], c_int),

@@ -5,3 +5,4 @@ from .sampler import DistributedSampler, shard_indices      # noqa: F401
 from .transforms import nearest_index_table, resize_labels_nearest   # noqa: F401
 from .transforms import (ColorJitter, JitterParams, adjust_brightness, adjust_contrast, adjust_hue,   # noqa: F401
                          adjust_saturation, color_jitter, crop_flip_normalize)
+from .transforms import BlurParams, RandomGaussianBlur, gaussian_blur, gaussian_taps   # noqa: F401

@@ -8,6 +8,7 @@ closed form floor((x+0.5)*scale) differs from that in the last bit for some
 sizes, so the tables below reproduce the running sum (np.cumsum adds
 sequentially, in the same order)."""
 import ctypes
+import random
 
 import numpy as np
 import torch
@@ -61,12 +62,15 @@ def resize_labels_nearest(mask, size):
 MEAN_STD = ([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])      # config.py:96-97 (cfg.DATASET.MEAN / STD)
 
 
-def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitter=None):
+def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitter=None, blur=None):
     """img_u8: uint8 CUDA [H,W,3] (RGB, as np.array(PIL image)); labels_u8: uint8 CUDA [H,W] or None;
     window = (x0, y0, w, h) as PIL's crop box origin + size; flip: mirror the cropped pair.
     jitter: None, or the JitterParams of ColorJitter.get_params -- the image-only augmentation the reference runs
     between the joint transforms and ToTensor (datasets/base_loader.py:141-142), applied to the window in the same
     launch that normalises it (ssa_jitter_luma_sum + ssa_jitter_crop_flip_normalize); the labels do not see it.
+    blur: None, or the BlurParams of RandomGaussianBlur.get_params -- the reference's --gblur step, which follows the
+    jitter (datasets/__init__.py:102): the window goes through ssa_gblur_crop_flip_normalize instead, which runs the
+    jitter program (if any; ssa_jitter_luma_sum first) on the pixels it stages, blurs and normalises in one launch.
     Returns (image [1,h,w,16] bf16 NHWC -- hand it to the network's trunk --, labels [1,h,w] int64)."""
     from .._lib import lib, check
     assert img_u8.dtype == torch.uint8 and img_u8.is_cuda and img_u8.dim() == 3 and img_u8.shape[2] == 3
@@ -74,7 +78,9 @@ def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitt
     H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
     x0, y0, cw, ch = (int(v) for v in window)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if jitter is not None:
+    if blur is not None:
+        out = _blur_normalize(img_u8, blur, (x0, y0, cw, ch), flip, jitter, mean_std)
+    elif jitter is not None:
         out = _jitter_normalize(img_u8, jitter, (x0, y0, cw, ch), flip, mean_std)
     else:
         mean = (ctypes.c_float * 3)(*mean_std[0])
@@ -315,6 +321,133 @@ class ColorJitter:
 
     def __call__(self, img_u8):
         return color_jitter(img_u8, self.get_params(self.brightness, self.contrast, self.saturation, self.hue))
+
+
+# ---------------------------------------------------------------------------------------------
+# RandomGaussianBlur on the device (transforms/transforms.py:154-162; datasets/__init__.py:102 appends it under
+# --gblur, after ColorJitter): skimage.filters.gaussian(np.array(img), sigma, multichannel=True) * 255 truncated to
+# uint8, bit-identical to SciPy's arithmetic (csrc/gblur.hip).  skimage's function is a wrapper: it converts the bytes
+# to float64 (byte_to_float64() below -- the ONE place where that conversion is stated) and calls
+# scipy.ndimage.gaussian_filter(image, [sigma, sigma, 0], mode='nearest', truncate=4.0).  The draw stays on the host
+# and consumes Python's `random` as the reference does; what travels to the kernel is the tap table.
+# ---------------------------------------------------------------------------------------------
+def byte_to_float64():
+    """float64[256]: what skimage's img_as_float makes of a uint8 image (skimage/util/dtype.py: np.multiply(image,
+    1. / 255, dtype=float64)).  It is a product by the rounded reciprocal, not a division: 24 of the 256 values differ
+    from b / 255 in the last bit."""
+    return np.multiply(np.arange(256, dtype=np.uint8), 1 / 255, dtype=np.float64)
+
+
+def gaussian_taps(sigma):
+    """-> (radius, float64[radius + 1]): the radius int(4 sigma + 0.5) of scipy.ndimage.gaussian_filter1d at
+    truncate=4.0 and the normalised weights at distance 0..radius, derived operation by operation as
+    scipy.ndimage._gaussian_kernel1d derives them (the kernel is symmetric: SciPy's reversal changes nothing).
+    ValueError when the radius is outside 1..5, i.e. for sigma outside about [0.125, 1.375): the reference draws
+    sigma from [0.15, 1.3)."""
+    sigma = float(sigma)
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError("gaussian_taps: sigma must be positive and finite, not %r" % sigma)
+    radius = int(4.0 * sigma + 0.5)
+    if not 1 <= radius <= 5:
+        raise ValueError("gaussian_taps: sigma %r gives the radius %d; the device blur covers 1..5" % (sigma, radius))
+    sigma2 = sigma * sigma
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    phi_x = phi_x / phi_x.sum()
+    return radius, np.ascontiguousarray(phi_x[radius:], dtype=np.float64)
+
+
+class BlurParams:
+    """One drawn RandomGaussianBlur: sigma, and the radius and weights it means."""
+    __slots__ = ("sigma", "radius", "weights")
+
+    def __init__(self, sigma):
+        self.sigma = float(sigma)
+        self.radius, self.weights = gaussian_taps(self.sigma)
+
+    def __repr__(self):
+        return "BlurParams(sigma=%r)" % self.sigma
+
+    def taps(self):
+        """-> the ssa_gblur_taps the kernel takes by value."""
+        from .._lib import GblurTaps
+        tp = GblurTaps()
+        tp.radius = self.radius
+        for j, w in enumerate(self.weights):
+            tp.w[j] = float(w)
+        return tp
+
+
+_GBLUR_LUT = {}
+
+
+def _gblur_lut(device):
+    key = str(device)
+    t = _GBLUR_LUT.get(key)
+    if t is None:
+        t = _GBLUR_LUT[key] = torch.from_numpy(byte_to_float64()).to(device)
+    return t
+
+
+def _blur_prepare(img_u8, blur, window, jitter):
+    """Checks, the table, and (with a jitter whose program has a contrast step) the luma sum -> the launch arguments
+    both blur entry points share.  Nothing here waits for the device."""
+    if not isinstance(blur, BlurParams):
+        blur = BlurParams(blur)                    # a bare sigma
+    if jitter is not None:
+        img_u8, geom, pg, counter = _jitter_prepare(img_u8, jitter, window)
+        pg = ctypes.byref(pg)
+    else:
+        if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+            raise ValueError("the image must be uint8 [H, W, 3]")
+        img_u8 = img_u8.contiguous()
+        H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+        x0, y0, cw, ch = (0, 0, W, H) if window is None else (int(v) for v in window)
+        if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= W and y0 + ch <= H):
+            raise ValueError("window %r is empty or not inside the %d x %d image" % ((x0, y0, cw, ch), W, H))
+        geom, pg, counter = (H, W, x0, y0, cw, ch), None, None
+    return img_u8, geom, pg, counter, blur.taps(), _gblur_lut(img_u8.device)
+
+
+def gaussian_blur(img_u8, sigma_or_params, window=None, flip=False, jitter=None):
+    """img_u8: uint8 CUDA [H,W,3]; sigma_or_params: sigma or BlurParams; window = (x0, y0, w, h) or None for the whole
+    image; flip: mirror; jitter: None or the JitterParams to apply first.  -> uint8 [h,w,3] = what the reference's
+    RandomGaussianBlur makes, at that sigma, of the cropped (mirrored, jittered) image: the blur sees the WINDOW's
+    edges, not the source's."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    img_u8, (H, W, x0, y0, cw, ch), pg, counter, taps, lut = _blur_prepare(img_u8, sigma_or_params, window, jitter)
+    out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=img_u8.device)
+    check(lib().ssa_gblur_u8(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), pg, hb._p(counter),
+                             ctypes.byref(taps), hb._p(lut), hb._p(out), hb._s()), "ssa_gblur_u8")
+    return out
+
+
+def _blur_normalize(img_u8, blur, window, flip, jitter=None, mean_std=MEAN_STD):
+    """The image half of crop_flip_normalize(..., blur=params): (luma sum +) the fused jitter / blur / normalise launch."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    img_u8, (H, W, x0, y0, cw, ch), pg, counter, taps, lut = _blur_prepare(img_u8, blur, window, jitter)
+    mean = (ctypes.c_float * 3)(*mean_std[0])
+    std = (ctypes.c_float * 3)(*mean_std[1])
+    out = torch.empty((1, ch, cw, 16), dtype=hb.ACT_DTYPE, device=img_u8.device)
+    check(lib().ssa_gblur_crop_flip_normalize(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), pg, hb._p(counter),
+                                              ctypes.byref(taps), hb._p(lut), mean, std, hb._p(out), 16, hb._s()),
+          "ssa_gblur_crop_flip_normalize")
+    return out
+
+
+class RandomGaussianBlur:
+    """transforms/transforms.py:154-162 for uint8 CUDA [H,W,3] images: the same single draw from Python's `random`, the
+    blur on the device."""
+
+    @staticmethod
+    def get_params():
+        """sigma = 0.15 + random.random() * 1.15 -> BlurParams."""
+        return BlurParams(0.15 + random.random() * 1.15)
+
+    def __call__(self, img_u8):
+        return gaussian_blur(img_u8, self.get_params())
 
 
 class DevicePrefetcher:

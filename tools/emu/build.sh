@@ -15,7 +15,7 @@ objs=""
 for f in "$SRC"/*.hip "$HERE/emu_runtime.cpp"; do
   o="$OUT/$(basename "$f" | sed 's/\.[a-z]*$//').o"
   objs="$objs $o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$SRC/common.h" -nt "$o" ] || [ "$SRC/conv_epilogue.h" -nt "$o" ] || [ "$SRC/group.h" -nt "$o" ] || \
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$SRC/common.h" -nt "$o" ] || [ "$SRC/conv_epilogue.h" -nt "$o" ] || [ "$SRC/group.h" -nt "$o" ] || [ "$SRC/jitter_device.h" -nt "$o" ] || \
      [ "$HERE/include/hip/hip_runtime.h" -nt "$o" ] || [ "$ROOT/include/semseg_hip.h" -nt "$o" ]; then
     $CXX $FLAGS -c "$f" -o "$o" &
     pids="$pids $!"
