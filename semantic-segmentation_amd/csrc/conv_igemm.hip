@@ -20,6 +20,26 @@
 // LDS is double buffered with the next stage's global loads issued before the
 // current stage's MFMAs.  LDS rows are padded to 80 bytes so the 16 lanes that
 // ds_read_b128 services together hit 16 distinct 16-byte slots.
+//
+// How the gather is addressed (forward / data-gradient kernel).  Everything that depends only on (row, tap) is computed
+// once before the K loop, the loop itself is additions and one bit test per piece:
+//   per row    the byte offset of (b, iy0, ix0) in the tensor (modulo 2^32: it may lie before the tensor, the offset of
+//              a tap inside the image never does) and a 32-bit tap-validity mask, bit kh * KW + kw set when the tap lies
+//              inside the image; a row past M has mask 0.
+//   per thread a K cursor (tap, its column kw, channel byte offset kc) with the running tap offset
+//              (kh * dil * W + kw * dil) * ldx * 2, advanced by additions at every tap boundary a stage crosses (several
+//              per stage when Cin < BK).
+//   a piece    address = base + row offset + tap offset + kc; validity = row mask & (1 << tap).
+//   filter     one invariant byte offset per row; the stage advances a SCALAR offset.  BK = 64 against a Kpad padded to
+//              32: the upper half of the last stage is cut by one scalar compare per stage.
+//   zero fill  raw buffer loads (descriptors built from readfirstlane'd inputs: base, the view's extent
+//              ((P - 1) * ldx + Cin) * 2 bytes): a piece that is invalid gets the offset 2^31, past the extent, and the
+//              hardware range check returns zeros -- no select on the loaded value, no mask carried to the LDS store.
+//              Chosen over the plain form (valid address + select at the LDS store; -DSSA_IGEMM_PLAIN, and the form the
+//              CPU emulation compiles) by instruction count and an A/B on the device: profiles/igemm_addr_notes.md.
+// Shapes outside this fast form take the general gather, which recomputes (iy, ix), the bounds and the 64-bit address
+// for every piece (template parameter GEN, chosen on the host in launch_fwd): more than 32 taps (7x7), `transposed`
+// with stride > 1 (zero-inserted rows: the tap offset is not linear in the tap), tensors or filters of 2 GB and above.
 #include "conv_epilogue.h"
 #include "group.h"
 #include "../../include/semseg_hip.h"
@@ -55,6 +75,30 @@ __device__ __forceinline__ void mma_stage(const bf16_t* __restrict__ As,
   }
 }
 
+#if !defined(SSA_IGEMM_PLAIN) && !defined(SSA_EMU)
+// Raw buffer loads: a 16-byte piece whose offset lies past the descriptor's extent reads as zeros (hardware range check).
+constexpr bool kIgemmBuf = true;
+constexpr unsigned kBufOut = 0x80000000u;        // past every extent the fast form takes (< 2^31 bytes)
+typedef unsigned ssa_v4u __attribute__((ext_vector_type(4)));
+struct BufRsrc { __amdgpu_buffer_rsrc_t r; };
+__device__ __forceinline__ BufRsrc buf_rsrc(const void* p, unsigned bytes) {
+  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  void* q = reinterpret_cast<void*>(((uintptr_t)hi << 32) | lo);
+  return BufRsrc{__builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000)};
+}
+__device__ __forceinline__ uint4 buf_load16(const BufRsrc& r, unsigned voff, unsigned soff) {
+  const ssa_v4u v = __builtin_amdgcn_raw_buffer_load_b128(r.r, (int)voff, (int)soff, 0);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+#else
+constexpr bool kIgemmBuf = false;
+constexpr unsigned kBufOut = 0u;
+struct BufRsrc { int r; };
+__device__ __forceinline__ BufRsrc buf_rsrc(const void*, unsigned) { return BufRsrc{0}; }
+__device__ __forceinline__ uint4 buf_load16(const BufRsrc&, unsigned, unsigned) { return make_uint4(0, 0, 0, 0); }
+#endif
+
 // ----------------------------------------------------------------------------
 // forward / dgrad kernel
 // ----------------------------------------------------------------------------
@@ -75,7 +119,8 @@ struct IgemmArgs {
 // tiles keep 32 (two workgroups per CU).  The packed filter rows stay padded to 32 (the last stage is masked).
 template <int MI, int NI> struct IgemmBK { static constexpr int value = MI * NI <= 2 ? 64 : 32; };
 
-template <int WGM, int WGN, int MI, int NI>
+// GEN: the general gather (every piece's pixel recomputed from (iy, ix)); false: the fast form (see the header comment).
+template <int WGM, int WGN, int MI, int NI, bool GEN = false>
 struct ConvIgemm {
   typedef IgemmArgs Args;
   static constexpr int BK = IgemmBK<MI, NI>::value;
@@ -105,29 +150,68 @@ struct ConvIgemm {
   const int HoWo = d.Ho * d.Wo;
   const int pc = tid % PPR, r0 = tid / PPR;
 
+  // Per-row gather state, computed once.  General form: the pixel's (iy0, ix0, image base).  Fast form: the BYTE offset
+  // of (b, iy0, ix0) -- modulo 2^32: it may lie before the tensor, the offset of a valid tap never does -- and the
+  // validity mask of the row's taps, bit kh * KW + kw (0 for a row past M or past the tile).
   int iy0[A_IT], ix0[A_IT], pb[A_IT];
+  unsigned aoff[A_IT], amk[A_IT];
 #pragma unroll
   for (int i = 0; i < A_IT; ++i) {
     const int r = r0 + i * RPP, m = m0 + r;
-    if (r < BM && m < M) {
-      const int b = m / HoWo, rem = m - b * HoWo;
-      const int oy = rem / d.Wo, ox = rem - oy * d.Wo;
-      if (d.transposed) { iy0[i] = oy - d.pad; ix0[i] = ox - d.pad; }
-      else { iy0[i] = oy * d.stride - d.pad; ix0[i] = ox * d.stride - d.pad; }
-      pb[i] = b * d.H * d.W;
+    const bool rv = r < BM && m < M;
+    const int mm = rv ? m : 0;
+    const int b = mm / HoWo, rem = mm - b * HoWo;
+    const int oy = rem / d.Wo, ox = rem - oy * d.Wo;
+    const int sy = d.transposed ? 1 : d.stride;
+    const int y0 = oy * sy - d.pad, x0 = ox * sy - d.pad;
+    if constexpr (GEN) {
+      iy0[i] = rv ? y0 : INT_MIN / 2; ix0[i] = rv ? x0 : INT_MIN / 2; pb[i] = b * d.H * d.W;
     } else {
-      iy0[i] = INT_MIN / 2; ix0[i] = INT_MIN / 2; pb[i] = 0;
+      unsigned xm = 0, mk = 0;
+      for (int t = 0; t < d.KW; ++t) xm |= ((unsigned)(x0 + t * d.dil) < (unsigned)d.W ? 1u : 0u) << t;
+      for (int t = 0; t < d.KH; ++t) mk |= ((unsigned)(y0 + t * d.dil) < (unsigned)d.H ? xm : 0u) << (t * d.KW);
+      amk[i] = rv ? mk : 0u;
+      aoff[i] = (unsigned)(b * d.H * d.W + y0 * d.W + x0) * (unsigned)d.ldx * 2u;
     }
   }
-  // this thread's K cursor: channel offset inside the tap, and the tap itself
+  // this thread's K cursor: channel offset inside the tap, and the tap itself.  Fast form: kc in bytes, the tap's
+  // index, its column kw and its byte offset (kh * dil * W + kw * dil) * ldx * 2, all advanced by additions.
   int kc, kh, kw;
+  unsigned tap = 0, tapoff = 0;
   {
     const int kpos = pc * 8;
-    const int tap = kpos / d.Cin;
-    kc = kpos - tap * d.Cin;
-    kh = tap / d.KW;
-    kw = tap - kh * d.KW;
+    const int t = kpos / d.Cin;
+    kc = kpos - t * d.Cin;
+    kh = t / d.KW;
+    kw = t - kh * d.KW;
+    if constexpr (!GEN) {
+      kc *= 2;
+      tap = (unsigned)t;
+      tapoff = (unsigned)(kh * d.dil * d.W + kw * d.dil) * (unsigned)d.ldx * 2u;
+    }
   }
+  const unsigned cin2 = (unsigned)d.Cin * 2u;
+  const unsigned colstep = (unsigned)d.dil * (unsigned)d.ldx * 2u;                                  // kw -> kw + 1
+  const unsigned rowstep = (unsigned)(d.dil * d.W - (d.KW - 1) * d.dil) * (unsigned)d.ldx * 2u;    // (kh, KW - 1) -> (kh + 1, 0)
+  const int ncross = (BK + d.Cin - 1) / d.Cin;        // a stage crosses at most this many tap boundaries
+  // filter rows: byte offset of (n, pc * 8); a row past Cout reads zeros (buffer form) or row 0, zeroed when it is staged
+  unsigned bo[B_IT];
+  bool bok[B_IT];
+#pragma unroll
+  for (int j = 0; j < B_IT; ++j) {
+    const int r = r0 + j * RPP, n = n0 + r;
+    bok[j] = (r < BN) && (n < d.Cout);
+    bo[j] = ((unsigned)(bok[j] ? n : 0) * (unsigned)d.Kpad + (unsigned)pc * 8u) * 2u;
+  }
+  // BK = 64 against a Kpad padded to 32: the upper half of the last stage lies past the filter row (the gathered operand
+  // is zero there: Kpad >= taps * Cin).  It loads zeros (buffer form) or reads the row's previous 32 and is staged as zeros.
+  const bool khi = BK == 64 && pc * 8 >= 32;
+  const bool ktail = BK == 64 && (d.Kpad & 32) != 0;
+  constexpr bool BUF = !GEN && kIgemmBuf;
+  const BufRsrc xrs = buf_rsrc(x, (unsigned)((d.B * d.H * d.W - 1) * d.ldx + d.Cin) * 2u);
+  const BufRsrc wrs = buf_rsrc(w, (unsigned)d.Cout * (unsigned)d.Kpad * 2u);
+  const unsigned char* xb = reinterpret_cast<const unsigned char*>(x);
+  const unsigned char* wb = reinterpret_cast<const unsigned char*>(w);
   const int tr_mask = (1 << tr_shift) - 1;
   const int nk = (d.Kpad + BK - 1) / BK;
   const int o_mul = a.o_mul, o_py = a.o_py, o_px = a.o_px, o_W = a.o_W, o_HW = a.o_HW;
@@ -141,61 +225,90 @@ struct ConvIgemm {
   // Global loads run PD - 1 K-stages ahead of the MFMAs, through a ring of PD register sets.  With one stage in
   // flight (the first version) a 32-deep K-step cost a full memory latency: these launches are small (a 64x64 tile
   // is two MFMAs per wave and K-step), so the loop ran at ~1 us per step whatever it computed (profiles/r03_notes.md).
-  // Every lane loads (pieces outside the image / past Cout read a valid address and are zeroed when they are staged):
-  // a select on the loaded value would put the wait inside the load phase.
+  // Every lane loads.  Buffer form: a piece outside the image / past Cout / past Kpad loads zeros (offset past the
+  // extent).  Plain and general forms: it reads a valid address and is zeroed when it is staged -- a select on the loaded
+  // value at the load would put the wait inside the load phase; amask[slot] carries what the store needs: general form,
+  // the validity bits of the slot's A pieces; plain form, the bit of the slot's tap (tested against the rows' masks again).
   constexpr int PD = 4;
   uint4 ra[PD][A_IT], rb[PD][B_IT];
-  unsigned amask[PD], bmask[PD];
+  unsigned amask[PD];
   auto gload = [&](int kt, int slot) {
-    const bool kvalid = kh < d.KH;
-    unsigned am = 0, bm = 0;
+    if constexpr (GEN) {
+      const bool kvalid = kh < d.KH;
+      unsigned am = 0;
 #pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-      int iy = iy0[i] + kh * d.dil, ix = ix0[i] + kw * d.dil;
-      bool ok = kvalid;
-      if (d.transposed) {
-        ok = ok && iy >= 0 && ix >= 0 && ((iy & tr_mask) == 0) && ((ix & tr_mask) == 0);
-        iy >>= tr_shift; ix >>= tr_shift;
-        ok = ok && iy < d.H && ix < d.W;
-      } else {
-        ok = ok && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
+      for (int i = 0; i < A_IT; ++i) {
+        int iy = iy0[i] + kh * d.dil, ix = ix0[i] + kw * d.dil;
+        bool ok = kvalid;
+        if (d.transposed) {
+          ok = ok && iy >= 0 && ix >= 0 && ((iy & tr_mask) == 0) && ((ix & tr_mask) == 0);
+          iy >>= tr_shift; ix >>= tr_shift;
+          ok = ok && iy < d.H && ix < d.W;
+        } else {
+          ok = ok && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
+        }
+        const long pix = ok ? (long)(pb[i] + iy * d.W + ix) : 0;
+        const bf16_t* p = x + pix * d.ldx + (ok ? kc : 0);
+        ra[slot][i] = *reinterpret_cast<const uint4*>(p);
+        am |= (ok ? 1u : 0u) << i;
       }
-      const long pix = ok ? (long)(pb[i] + iy * d.W + ix) : 0;
-      const bf16_t* p = x + pix * d.ldx + (ok ? kc : 0);
-      ra[slot][i] = *reinterpret_cast<const uint4*>(p);
-      am |= (ok ? 1u : 0u) << i;
-    }
+      amask[slot] = am;
+      kc += BK;
+      while (kc >= d.Cin) {
+        kc -= d.Cin;
+        if (++kw == d.KW) { kw = 0; ++kh; }
+      }
+    } else {
+      const unsigned tbit = tap < 32u ? 1u << tap : 0u;
+      const unsigned koff = tapoff + (unsigned)kc;
 #pragma unroll
-    for (int j = 0; j < B_IT; ++j) {
-      const int r = r0 + j * RPP, n = n0 + r;
-      const bool ok = (r < BN) && (n < d.Cout) && (kt * BK + pc * 8 < d.Kpad);
-      const bf16_t* p = w + (ok ? (long)n * d.Kpad + kt * BK + pc * 8 : 0);
-      rb[slot][j] = *reinterpret_cast<const uint4*>(p);
-      bm |= (ok ? 1u : 0u) << j;
+      for (int i = 0; i < A_IT; ++i) {
+        const unsigned off = (amk[i] & tbit) ? aoff[i] + koff : kBufOut;
+        if constexpr (BUF) ra[slot][i] = buf_load16(xrs, off, 0u);
+        else ra[slot][i] = *reinterpret_cast<const uint4*>(xb + off);
+      }
+      amask[slot] = tbit;
+      // advance the cursor by one stage: every boundary crossed is a select and an addition
+      kc += BK * 2;
+      for (int c = 0; c < ncross; ++c) {
+        const bool cr = (unsigned)kc >= cin2;
+        const bool wrap = cr && kw + 1 == d.KW;
+        kc -= cr ? (int)cin2 : 0;
+        tapoff += cr ? (wrap ? rowstep : colstep) : 0u;
+        kw = wrap ? 0 : kw + (cr ? 1 : 0);
+        tap += cr ? 1u : 0u;
+      }
     }
-    amask[slot] = am;
-    bmask[slot] = bm;
-    // advance the cursor by one stage
-    kc += BK;
-    while (kc >= d.Cin) {
-      kc -= d.Cin;
-      if (++kw == d.KW) { kw = 0; ++kh; }
+    if constexpr (BUF) {
+      const bool cut = ktail && khi && kt == nk - 1;
+#pragma unroll
+      for (int j = 0; j < B_IT; ++j)
+        rb[slot][j] = buf_load16(wrs, (cut || !bok[j]) ? kBufOut : bo[j], (unsigned)kt * (BK * 2));
+    } else {
+      const unsigned char* wk = wb + (size_t)kt * (BK * 2);
+      const unsigned back = (ktail && khi && kt == nk - 1) ? 64u : 0u;
+#pragma unroll
+      for (int j = 0; j < B_IT; ++j)
+        rb[slot][j] = *reinterpret_cast<const uint4*>(wk + (bo[j] - back));
     }
   };
-  auto lstore = [&](int buf, int slot) {
+  // stages the ring slot of K-stage kt
+  auto lstore = [&](int buf, int slot, int kt) {
     bf16_t* As = lds + buf * STAGE;
     bf16_t* Bs = As + BM * LDT;
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
       const int r = r0 + i * RPP;
-      if (r < BM)
-        *reinterpret_cast<uint4*>(As + r * LDT + pc * 8) = ((amask[slot] >> i) & 1u) ? ra[slot][i] : make_uint4(0, 0, 0, 0);
+      const bool ok = BUF || (GEN ? ((amask[slot] >> i) & 1u) != 0 : (amk[i] & amask[slot]) != 0);
+      if (BM % RPP == 0 || r < BM)
+        *reinterpret_cast<uint4*>(As + r * LDT + pc * 8) = ok ? ra[slot][i] : make_uint4(0, 0, 0, 0);
     }
+    const bool kcut = ktail && khi && kt == nk - 1;
 #pragma unroll
     for (int j = 0; j < B_IT; ++j) {
       const int r = r0 + j * RPP;
-      if (r < BN)
-        *reinterpret_cast<uint4*>(Bs + r * LDT + pc * 8) = ((bmask[slot] >> j) & 1u) ? rb[slot][j] : make_uint4(0, 0, 0, 0);
+      if (BN % RPP == 0 || r < BN)
+        *reinterpret_cast<uint4*>(Bs + r * LDT + pc * 8) = (BUF || (bok[j] && !kcut)) ? rb[slot][j] : make_uint4(0, 0, 0, 0);
     }
   };
 
@@ -210,7 +323,7 @@ struct ConvIgemm {
 #pragma unroll
   for (int j = 0; j < PD - 1; ++j)
     if (j < nk) gload(j, j);
-  lstore(0, 0);
+  lstore(0, 0, 0);
   __syncthreads();
   for (int kt0 = 0; kt0 < nk; kt0 += PD) {
 #pragma unroll
@@ -221,7 +334,7 @@ struct ConvIgemm {
         if (kt + PD - 1 < nk) gload(kt + PD - 1, (j + PD - 1) % PD);
         const bf16_t* As = lds + buf * STAGE;
         mma_stage<MI, NI, BK, LDT>(As, As + BM * LDT, wm * MI * 32, wn * NI * 32, lane, acc);
-        if (kt + 1 < nk) lstore(buf ^ 1, (j + 1) % PD);
+        if (kt + 1 < nk) lstore(buf ^ 1, (j + 1) % PD, kt + 1);
         __syncthreads();
       }
     }
@@ -843,7 +956,13 @@ int launch_fwd(const ssa_conv_desc& d, const void* x, const void* w, const float
   a.o_mul = om ? om->mul : 0; a.o_py = om ? om->py : 0; a.o_px = om ? om->px : 0;
   a.o_W = om ? om->W : 0; a.o_HW = om ? om->HW : 0;
   a.aff = g_affine.aff; a.res = g_affine.res; a.ldres = g_affine.ldres; a.relu = g_affine.relu;
-  return ssa::submit<ConvIgemm<WGM, WGN, MI, NI>>(a, tiles_m * tiles_n, 1, lds, s);
+  if ((long)d.Cout * d.Kpad * 2 >= (1L << 32)) return SSA_EUNSUPPORTED;      // filter rows are addressed by 32-bit byte offsets
+  // the fast gather: a tap-validity mask of 32 bits per row, tap offsets linear in (kh, kw), 32-bit byte offsets with
+  // 2^31 free as the out-of-range offset
+  const long x_bytes = (((long)d.B * d.H * d.W - 1) * d.ldx + d.Cin) * 2;
+  const bool fast = d.KH * d.KW <= 32 && !(d.transposed && d.stride > 1) && x_bytes < (1L << 31) && (long)d.Cout * d.Kpad * 2 < (1L << 31);
+  if (fast) return ssa::submit<ConvIgemm<WGM, WGN, MI, NI, false>>(a, tiles_m * tiles_n, 1, lds, s);
+  return ssa::submit<ConvIgemm<WGM, WGN, MI, NI, true>>(a, tiles_m * tiles_n, 1, lds, s);
 }
 
 template <int WGM, int WGN, int MI, int NI>

@@ -1,5 +1,7 @@
 """Run a tool / bench.py against an experiment build of the library (tools/expbuild.sh):
-python tools/libvariant.py <name> <script.py> [args...]   -> lib/libsemseg_hip_<name>.so"""
+python tools/libvariant.py <name> <script.py> [args...]   -> lib/libsemseg_hip_<name>.so
+(fp16 storage, SSA_ACT_DTYPE=fp16 in the environment: lib/libsemseg_hip_f16_<name>.so; bench.py's own default of fp16 is
+set after this module has chosen the library, so name the storage format explicitly)"""
 import os
 import runpy
 import sys
@@ -10,6 +12,6 @@ for p in (ROOT, os.path.join(ROOT, "semantic-segmentation_amd")):
 from semseg_amd import _lib  # noqa: E402
 
 name, script = sys.argv[1], sys.argv[2]
-_lib.LIB_PATH = _lib.LIB_PATH.replace("libsemseg_hip.so", "libsemseg_hip_%s.so" % name)
+_lib.LIB_PATH = _lib.LIB_PATH[:-len(".so")] + "_%s.so" % name
 sys.argv = [script] + sys.argv[3:]
 runpy.run_path(script, run_name="__main__")
