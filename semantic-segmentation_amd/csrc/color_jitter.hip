@@ -14,9 +14,7 @@
 // needs no host synchronisation and can be captured into a graph.
 // Byte streaming, HBM-bound: 3 B read per pixel per kernel; 3 B (uint8) or 32 B (normalised NHWC, 16-channel
 // padded, the trunk's input) written.
-#include "common.h"
-#include "../../include/semseg_hip.h"
-#include "jitter_device.h"
+#include "input_tail.h"
 
 // Every product and sum in this file is rounded on its own, as the C code Pillow was compiled from rounds them: no
 // contraction to FMA.  hipcc contracts by default, across statements and through inlined functions, and the
@@ -26,8 +24,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-
-struct Norm3 { float mean[3], stdv[3]; };
 
 // Zeroes the counter in stream order, as a kernel node of its own: captured into a graph with the luma sum and the apply,
 // it clears the word at the start of every replay.
@@ -51,50 +47,6 @@ __global__ __launch_bounds__(256) void jitter_luma_sum_kernel(const unsigned cha
   if (threadIdx.x == 0) atomicAdd(counter, red[0] + red[1] + red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void jitter_apply_u8_kernel(const unsigned char* __restrict__ img, int W, int x0,
-                                                              int y0, int cw, int ch, int flip, ssa_jitter_program pg,
-                                                              const unsigned long long* __restrict__ counter,
-                                                              unsigned char* __restrict__ out) {
-  const long n = (long)cw * ch;
-  const int m = contrast_mean(pg, counter, n);
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int y = (int)(i / cw), x = (int)(i - (long)y * cw);
-    const int sx = x0 + (flip ? cw - 1 - x : x), sy = y0 + y;
-    const unsigned char* p = img + ((long)sy * W + sx) * 3;
-    int r = p[0], g = p[1], b = p[2];
-    jitter_pixel(pg, m, r, g, b);
-    unsigned char* o = out + i * 3;
-    o[0] = (unsigned char)r;
-    o[1] = (unsigned char)g;
-    o[2] = (unsigned char)b;
-  }
-}
-
-// The same program followed by the arithmetic and the store of image_crop_flip_normalize_kernel (input_pipeline.hip)
-__global__ __launch_bounds__(256) void jitter_crop_flip_normalize_kernel(
-    const unsigned char* __restrict__ img, int W, int x0, int y0, int cw, int ch, int flip, ssa_jitter_program pg,
-    const unsigned long long* __restrict__ counter, Norm3 nm, bf16_t* __restrict__ out, int cpad) {
-  const long n = (long)cw * ch;
-  const int m = contrast_mean(pg, counter, n);
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int y = (int)(i / cw), x = (int)(i - (long)y * cw);
-    const int sx = x0 + (flip ? cw - 1 - x : x), sy = y0 + y;
-    const unsigned char* p = img + ((long)sy * W + sx) * 3;
-    int c3[3] = {p[0], p[1], p[2]};
-    jitter_pixel(pg, m, c3[0], c3[1], c3[2]);
-    bf16_t* o = out + i * cpad;
-    float f[8];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) f[c] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)c3[c], 255.f), nm.mean[c]), nm.stdv[c]);
-#pragma unroll
-    for (int c = 3; c < 8; ++c) f[c] = 0.f;
-    *reinterpret_cast<uint4*>(o) = pack8(f);
-    for (int c0 = 8; c0 < cpad; c0 += 8) *reinterpret_cast<uint4*>(o + c0) = make_uint4(0, 0, 0, 0);
-  }
-}
-
-int blocks_for(long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
-
 }  // namespace
 
 extern "C" {
@@ -107,7 +59,7 @@ int ssa_jitter_luma_sum(const unsigned char* img_hwc, int H, int W, int x0, int 
   if (!counter || (reinterpret_cast<uintptr_t>(counter) & 7u)) return SSA_EINVAL;
   hipLaunchKernelGGL(jitter_clear_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, counter);
   SSA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jitter_luma_sum_kernel, dim3(blocks_for((long)cw * ch)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(jitter_luma_sum_kernel, dim3(stream_blocks((long)cw * ch)), dim3(256), 0, (hipStream_t)stream,
                      img_hwc, W, x0, y0, cw, ch, *program, counter);
   SSA_LAUNCH_CHECK();
   return SSA_OK;
@@ -119,10 +71,8 @@ int ssa_jitter_apply_u8(const unsigned char* img_hwc, int H, int W, int x0, int 
   bool contrast = false;
   if (!img_hwc || !out_hwc || !program_ok(program, &contrast) || !window_ok(H, W, x0, y0, cw, ch)) return SSA_EINVAL;
   if (contrast && (!counter || (reinterpret_cast<uintptr_t>(counter) & 7u))) return SSA_EINVAL;
-  hipLaunchKernelGGL(jitter_apply_u8_kernel, dim3(blocks_for((long)cw * ch)), dim3(256), 0, (hipStream_t)stream,
-                     img_hwc, W, x0, y0, cw, ch, flip ? 1 : 0, *program, counter, out_hwc);
-  SSA_LAUNCH_CHECK();
-  return SSA_OK;
+  return tail_stream_launch<true, false>(img_hwc, W, x0, y0, cw, ch, flip, Norm3{}, out_hwc, 0, *program, counter,
+                                         stream);
 }
 
 int ssa_jitter_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, int x0, int y0, int cw, int ch,
@@ -130,22 +80,13 @@ int ssa_jitter_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, i
                                    const float* mean3, const float* std3, void* out_nhwc_bf16, int cpad,
                                    void* stream) {
   bool contrast = false;
-  if (!img_hwc || !out_nhwc_bf16 || !mean3 || !std3 || !program_ok(program, &contrast) ||
-      !window_ok(H, W, x0, y0, cw, ch))
+  Norm3 nm;
+  if (!img_hwc || !out_nhwc_bf16 || !program_ok(program, &contrast) || !window_ok(H, W, x0, y0, cw, ch) ||
+      !norm3_ok(mean3, std3, out_nhwc_bf16, cpad, &nm))
     return SSA_EINVAL;
   if (contrast && (!counter || (reinterpret_cast<uintptr_t>(counter) & 7u))) return SSA_EINVAL;
-  if (cpad < 8 || cpad % 8 || (reinterpret_cast<uintptr_t>(out_nhwc_bf16) & 15u)) return SSA_EINVAL;
-  Norm3 nm;
-  for (int c = 0; c < 3; ++c) {
-    if (!(std3[c] > 0.f)) return SSA_EINVAL;
-    nm.mean[c] = mean3[c];
-    nm.stdv[c] = std3[c];
-  }
-  hipLaunchKernelGGL(jitter_crop_flip_normalize_kernel, dim3(blocks_for((long)cw * ch)), dim3(256), 0,
-                     (hipStream_t)stream, img_hwc, W, x0, y0, cw, ch, flip ? 1 : 0, *program, counter, nm,
-                     (bf16_t*)out_nhwc_bf16, cpad);
-  SSA_LAUNCH_CHECK();
-  return SSA_OK;
+  return tail_stream_launch<true, true>(img_hwc, W, x0, y0, cw, ch, flip, nm, out_nhwc_bf16, cpad, *program, counter,
+                                        stream);
 }
 
 }  // extern "C"

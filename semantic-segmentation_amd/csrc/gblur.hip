@@ -20,9 +20,7 @@
 // stores either the bytes (ssa_gblur_u8) or what ssa_image_u8_crop_flip_normalize makes of them
 // (ssa_gblur_crop_flip_normalize).  Per pixel 3 B read (halo overlap served by L2) and 3 B or 32 B written; 39 KB of
 // static LDS.
-#include "common.h"
-#include "../../include/semseg_hip.h"
-#include "jitter_device.h"
+#include "input_tail.h"
 
 // Every product and sum below is rounded on its own, as the C code SciPy was compiled from rounds them: hipcc
 // contracts a * b + c to one v_fma_f64 by default, across statements and through inlined functions.
@@ -33,8 +31,6 @@ namespace {
 constexpr int TH = 16, TW = 64, RMAX = 5;       // tile of the window, largest radius
 constexpr int HH = TH + 2 * RMAX;               // staged rows
 constexpr int HROW = (TW + 2 * RMAX) * 3;       // staged channel values per row (222)
-
-struct Norm3 { float mean[3], stdv[3]; };
 
 // One pass at one position: x(0) loads the centre, x(-j * stride) and x(j * stride) the pair at distance j
 template <typename Load>
@@ -97,19 +93,11 @@ __global__ __launch_bounds__(256) void gblur_kernel(const unsigned char* __restr
       if (y < ch && xb < (long)cw * 3) o[(long)y * cw * 3 + xb] = s_out[i];
     }
   } else {
-    // the arithmetic and the store of image_crop_flip_normalize_kernel (input_pipeline.hip)
     for (int i = tid; i < TH * TW; i += 256) {
       const int r = i / TW, x = i - r * TW;
       if (ty + r >= ch || tx + x >= cw) continue;
       const unsigned char* p = s_out + i * 3;
-      bf16_t* o = (bf16_t*)out + ((long)(ty + r) * cw + tx + x) * cpad;
-      float f[8];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) f[c] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)p[c], 255.f), nm.mean[c]), nm.stdv[c]);
-#pragma unroll
-      for (int c = 3; c < 8; ++c) f[c] = 0.f;
-      *reinterpret_cast<uint4*>(o) = pack8(f);
-      for (int c0 = 8; c0 < cpad; c0 += 8) *reinterpret_cast<uint4*>(o + c0) = make_uint4(0, 0, 0, 0);
+      store_normalized(p[0], p[1], p[2], nm, (bf16_t*)out + ((long)(ty + r) * cw + tx + x) * cpad, cpad);
     }
   }
 }
@@ -155,15 +143,10 @@ int ssa_gblur_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, in
                                   const ssa_gblur_taps* taps, const double* lut256, const float* mean3,
                                   const float* std3, void* out_nhwc, int cpad, void* stream) {
   ssa_jitter_program pg;
-  if (!mean3 || !std3 || !gblur_args_ok(img_hwc, H, W, x0, y0, cw, ch, program, counter, taps, lut256, out_nhwc, &pg))
-    return SSA_EINVAL;
-  if (cpad != 16 || (reinterpret_cast<uintptr_t>(out_nhwc) & 15u)) return SSA_EINVAL;
   Norm3 nm;
-  for (int c = 0; c < 3; ++c) {
-    if (!(std3[c] > 0.f)) return SSA_EINVAL;
-    nm.mean[c] = mean3[c];
-    nm.stdv[c] = std3[c];
-  }
+  if (!gblur_args_ok(img_hwc, H, W, x0, y0, cw, ch, program, counter, taps, lut256, out_nhwc, &pg) || cpad != 16 ||
+      !norm3_ok(mean3, std3, out_nhwc, cpad, &nm))
+    return SSA_EINVAL;
   hipLaunchKernelGGL(gblur_kernel<true>, gblur_grid(cw, ch), dim3(256), 0, (hipStream_t)stream, img_hwc, W, x0, y0,
                      cw, ch, flip ? 1 : 0, pg, counter, *taps, lut256, nm, out_nhwc, cpad);
   SSA_LAUNCH_CHECK();

@@ -1,7 +1,7 @@
 // The per-pixel steps of the device ColorJitter, shared by color_jitter.hip (which states the arithmetic) and gblur.hip
 // (which runs them on every pixel it stages): Pillow's luma, Image.blend, the HSV round trip of adjust_hue, the
-// program interpreter and the contrast mean read from the luma counter, plus the host-side checks of a window and of a
-// program.  Every product and sum is rounded on its own (see color_jitter.hip): the functions that multiply and add
+// program interpreter and the contrast mean read from the luma counter, plus the host-side check of a program (the
+// streaming kernel that runs them is in input_tail.h).  Every product and sum is rounded on its own (see color_jitter.hip): the functions that multiply and add
 // carry the pragma themselves, so they stay uncontracted whatever the including file is compiled under.
 #pragma once
 #include <cmath>
@@ -92,10 +92,6 @@ __device__ __forceinline__ int contrast_mean(const ssa_jitter_program& pg, const
   for (int k = 0; k < pg.n_ops; ++k)
     if (pg.op[k] == SSA_JITTER_CONTRAST) return (int)((double)*counter / (double)n + 0.5);
   return 0;
-}
-
-bool window_ok(int H, int W, int x0, int y0, int cw, int ch) {
-  return H > 0 && W > 0 && cw > 0 && ch > 0 && x0 >= 0 && y0 >= 0 && (long)x0 + cw <= W && (long)y0 + ch <= H;
 }
 
 // 0..4 distinct known op codes and finite factors (blend converts f * (x - d) + d to int: undefined for NaN and infinity);

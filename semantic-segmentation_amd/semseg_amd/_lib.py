@@ -29,8 +29,8 @@ def source_sha():
     binary (ssa_source_sha).  None if the sources are not there (a binary-only installation)."""
     import glob
     import hashlib
-    # (the same files in the same order as SRCS + HDRS of csrc/Makefile)
-    files = sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + [os.path.join(CSRC, h) for h in ("common.h", "conv_epilogue.h", "group.h", "jitter_device.h")] + [
+    # (the same files in the same order as SRCS + HDRS of csrc/Makefile: every *.hip, then every *.h, sorted bytewise)
+    files = sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [
         os.path.normpath(os.path.join(_HERE, "..", "..", "include", "semseg_hip.h"))]
     if not files or not all(os.path.exists(f) for f in files):
         return None

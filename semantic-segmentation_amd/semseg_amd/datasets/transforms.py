@@ -74,22 +74,10 @@ def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitt
     Returns (image [1,h,w,16] bf16 NHWC -- hand it to the network's trunk --, labels [1,h,w] int64)."""
     from .._lib import lib, check
     assert img_u8.dtype == torch.uint8 and img_u8.is_cuda and img_u8.dim() == 3 and img_u8.shape[2] == 3
-    img_u8 = img_u8.contiguous()
     H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
     x0, y0, cw, ch = (int(v) for v in window)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if blur is not None:
-        out = _blur_normalize(img_u8, blur, (x0, y0, cw, ch), flip, jitter, mean_std)
-    elif jitter is not None:
-        out = _jitter_normalize(img_u8, jitter, (x0, y0, cw, ch), flip, mean_std)
-    else:
-        mean = (ctypes.c_float * 3)(*mean_std[0])
-        std = (ctypes.c_float * 3)(*mean_std[1])
-        from ..hip_backend import ACT_DTYPE
-        out = torch.empty((1, ch, cw, 16), dtype=ACT_DTYPE, device=img_u8.device)
-        check(lib().ssa_image_u8_crop_flip_normalize(ctypes.c_void_p(img_u8.data_ptr()), H, W, x0, y0, cw, ch,
-                                                     int(bool(flip)), mean, std, ctypes.c_void_p(out.data_ptr()), 16,
-                                                     stream), "ssa_image_u8_crop_flip_normalize")
+    out = _image_half(img_u8, (x0, y0, cw, ch), flip, jitter, blur, True, mean_std)
     gts = None
     if labels_u8 is not None:
         assert labels_u8.dtype == torch.uint8 and labels_u8.is_cuda and tuple(labels_u8.shape) == (H, W)
@@ -99,6 +87,54 @@ def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitt
                                            int(bool(flip)), ctypes.c_void_p(gts.data_ptr()), stream),
               "ssa_label_u8_crop_flip")
     return out, gts
+
+
+# (blur?, jitter?, normalised output?) -> the entry point.  Both blur entry points take the program as an optional
+# argument; a window that is neither jittered nor blurred has no uint8 form.
+_IMAGE_ENTRY = {(False, False, True): "ssa_image_u8_crop_flip_normalize",
+                (False, True, False): "ssa_jitter_apply_u8", (False, True, True): "ssa_jitter_crop_flip_normalize",
+                (True, False, False): "ssa_gblur_u8", (True, False, True): "ssa_gblur_crop_flip_normalize",
+                (True, True, False): "ssa_gblur_u8", (True, True, True): "ssa_gblur_crop_flip_normalize"}
+
+
+def _image_half(img_u8, window, flip, jitter=None, blur=None, normalize=True, mean_std=MEAN_STD):
+    """The image half of the tail for every combination: the window (None: the whole image) of img_u8, mirrored under
+    `flip`, through the jitter program (JitterParams or None), the blur (BlurParams, a bare sigma or None) and, under
+    `normalize`, ToTensor + Normalize -> [1,h,w,16] in the activation type, else uint8 [h,w,3].  One launch, after the
+    luma sum where the program has a contrast step; the mean itself is formed on the device: nothing here waits."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    if blur is not None and not isinstance(blur, BlurParams):
+        blur = BlurParams(blur)
+    if jitter is not None and not isinstance(jitter, JitterParams):
+        raise TypeError("jitter parameters must be a JitterParams (ColorJitter.get_params), not %r" % type(jitter))
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        raise ValueError("the image must be uint8 [H, W, 3]")
+    img_u8 = img_u8.contiguous()
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    x0, y0, cw, ch = (0, 0, W, H) if window is None else (int(v) for v in window)
+    if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= W and y0 + ch <= H):
+        raise ValueError("window %r is empty or not inside the %d x %d image" % ((x0, y0, cw, ch), W, H))
+    name = _IMAGE_ENTRY[blur is not None, jitter is not None, bool(normalize)]
+    args = [hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip))]
+    if jitter is not None:
+        pg, counter = jitter.program(), None
+        if "contrast" in jitter.order:
+            counter = torch.empty((1,), dtype=torch.int64, device=img_u8.device)
+            check(lib().ssa_jitter_luma_sum(*args[:7], ctypes.byref(pg), hb._p(counter), hb._s()), "ssa_jitter_luma_sum")
+        args += [ctypes.byref(pg), hb._p(counter)]
+    elif blur is not None:
+        args += [None, None]
+    if blur is not None:
+        args += [ctypes.byref(blur.taps()), hb._p(_gblur_lut(img_u8.device))]
+    if normalize:
+        out = torch.empty((1, ch, cw, 16), dtype=hb.ACT_DTYPE, device=img_u8.device)
+        args += [(ctypes.c_float * 3)(*mean_std[0]), (ctypes.c_float * 3)(*mean_std[1]), hb._p(out), 16]
+    else:
+        out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=img_u8.device)
+        args.append(hb._p(out))
+    check(getattr(lib(), name)(*args, hb._s()), name)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -216,55 +252,14 @@ class JitterParams:
         return pg
 
 
-def _jitter_prepare(img_u8, params, window):
-    """Checks + the luma sum the contrast step needs (no launch without one) -> the launch arguments both apply
-    kernels share.  The mean itself is formed on the device: nothing here waits for the sum."""
-    from .. import hip_backend as hb
-    from .._lib import lib, check
-    if not isinstance(params, JitterParams):
-        raise TypeError("jitter parameters must be a JitterParams (ColorJitter.get_params), not %r" % type(params))
-    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
-        raise ValueError("the image must be uint8 [H, W, 3]")
-    img_u8 = img_u8.contiguous()
-    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
-    x0, y0, cw, ch = (0, 0, W, H) if window is None else (int(v) for v in window)
-    if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= W and y0 + ch <= H):
-        raise ValueError("window %r is empty or not inside the %d x %d image" % ((x0, y0, cw, ch), W, H))
-    pg = params.program()
-    counter = None
-    if "contrast" in params.order:
-        counter = torch.empty((1,), dtype=torch.int64, device=img_u8.device)
-        check(lib().ssa_jitter_luma_sum(hb._p(img_u8), H, W, x0, y0, cw, ch, ctypes.byref(pg), hb._p(counter), hb._s()),
-              "ssa_jitter_luma_sum")
-    return img_u8, (H, W, x0, y0, cw, ch), pg, counter
-
-
 def color_jitter(img_u8, params, window=None, flip=False):
     """img_u8: uint8 CUDA [H,W,3]; params: JitterParams; window = (x0, y0, w, h) or None for the whole image; flip:
     mirror the result.  -> uint8 [h,w,3] = the drawn transform applied to the cropped image, as
     ColorJitter.get_params(...)(img.crop(...)) followed by FLIP_LEFT_RIGHT gives it (the contrast mean is taken over
     the window and does not depend on the flip)."""
-    from .. import hip_backend as hb
-    from .._lib import lib, check
-    img_u8, (H, W, x0, y0, cw, ch), pg, counter = _jitter_prepare(img_u8, params, window)
-    out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=img_u8.device)
-    check(lib().ssa_jitter_apply_u8(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), ctypes.byref(pg),
-                                    hb._p(counter), hb._p(out), hb._s()), "ssa_jitter_apply_u8")
-    return out
-
-
-def _jitter_normalize(img_u8, params, window, flip, mean_std=MEAN_STD):
-    """The image half of crop_flip_normalize(..., jitter=params): luma sum + the fused apply / normalise launch."""
-    from .. import hip_backend as hb
-    from .._lib import lib, check
-    img_u8, (H, W, x0, y0, cw, ch), pg, counter = _jitter_prepare(img_u8, params, window)
-    mean = (ctypes.c_float * 3)(*mean_std[0])
-    std = (ctypes.c_float * 3)(*mean_std[1])
-    out = torch.empty((1, ch, cw, 16), dtype=hb.ACT_DTYPE, device=img_u8.device)
-    check(lib().ssa_jitter_crop_flip_normalize(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), ctypes.byref(pg),
-                                               hb._p(counter), mean, std, hb._p(out), 16, hb._s()),
-          "ssa_jitter_crop_flip_normalize")
-    return out
+    if not isinstance(params, JitterParams):
+        raise TypeError("jitter parameters must be a JitterParams (ColorJitter.get_params), not %r" % type(params))
+    return _image_half(img_u8, window, flip, params, None, False)
 
 
 def adjust_brightness(img_u8, brightness_factor):
@@ -389,52 +384,12 @@ def _gblur_lut(device):
     return t
 
 
-def _blur_prepare(img_u8, blur, window, jitter):
-    """Checks, the table, and (with a jitter whose program has a contrast step) the luma sum -> the launch arguments
-    both blur entry points share.  Nothing here waits for the device."""
-    if not isinstance(blur, BlurParams):
-        blur = BlurParams(blur)                    # a bare sigma
-    if jitter is not None:
-        img_u8, geom, pg, counter = _jitter_prepare(img_u8, jitter, window)
-        pg = ctypes.byref(pg)
-    else:
-        if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
-            raise ValueError("the image must be uint8 [H, W, 3]")
-        img_u8 = img_u8.contiguous()
-        H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
-        x0, y0, cw, ch = (0, 0, W, H) if window is None else (int(v) for v in window)
-        if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= W and y0 + ch <= H):
-            raise ValueError("window %r is empty or not inside the %d x %d image" % ((x0, y0, cw, ch), W, H))
-        geom, pg, counter = (H, W, x0, y0, cw, ch), None, None
-    return img_u8, geom, pg, counter, blur.taps(), _gblur_lut(img_u8.device)
-
-
 def gaussian_blur(img_u8, sigma_or_params, window=None, flip=False, jitter=None):
     """img_u8: uint8 CUDA [H,W,3]; sigma_or_params: sigma or BlurParams; window = (x0, y0, w, h) or None for the whole
     image; flip: mirror; jitter: None or the JitterParams to apply first.  -> uint8 [h,w,3] = what the reference's
     RandomGaussianBlur makes, at that sigma, of the cropped (mirrored, jittered) image: the blur sees the WINDOW's
     edges, not the source's."""
-    from .. import hip_backend as hb
-    from .._lib import lib, check
-    img_u8, (H, W, x0, y0, cw, ch), pg, counter, taps, lut = _blur_prepare(img_u8, sigma_or_params, window, jitter)
-    out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=img_u8.device)
-    check(lib().ssa_gblur_u8(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), pg, hb._p(counter),
-                             ctypes.byref(taps), hb._p(lut), hb._p(out), hb._s()), "ssa_gblur_u8")
-    return out
-
-
-def _blur_normalize(img_u8, blur, window, flip, jitter=None, mean_std=MEAN_STD):
-    """The image half of crop_flip_normalize(..., blur=params): (luma sum +) the fused jitter / blur / normalise launch."""
-    from .. import hip_backend as hb
-    from .._lib import lib, check
-    img_u8, (H, W, x0, y0, cw, ch), pg, counter, taps, lut = _blur_prepare(img_u8, blur, window, jitter)
-    mean = (ctypes.c_float * 3)(*mean_std[0])
-    std = (ctypes.c_float * 3)(*mean_std[1])
-    out = torch.empty((1, ch, cw, 16), dtype=hb.ACT_DTYPE, device=img_u8.device)
-    check(lib().ssa_gblur_crop_flip_normalize(hb._p(img_u8), H, W, x0, y0, cw, ch, int(bool(flip)), pg, hb._p(counter),
-                                              ctypes.byref(taps), hb._p(lut), mean, std, hb._p(out), 16, hb._s()),
-          "ssa_gblur_crop_flip_normalize")
-    return out
+    return _image_half(img_u8, window, flip, jitter, sigma_or_params, False)
 
 
 class RandomGaussianBlur:

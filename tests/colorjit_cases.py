@@ -40,9 +40,9 @@ def run_u8(dev, img, p, window=None, flip=False):
 
 def run_fused(dev, img, p, window, flip):
     """The image half of crop_flip_normalize(..., jitter=p) -> CPU tensor [h, w, 16]."""
-    from semseg_amd.datasets.transforms import _jitter_normalize
+    from semseg_amd.datasets.transforms import _image_half
     h, w = img.shape[:2]
-    return _jitter_normalize(torch.from_numpy(img).to(dev), p, window or (0, 0, w, h), flip)[0].cpu()
+    return _image_half(torch.from_numpy(img).to(dev), window or (0, 0, w, h), flip, p)[0].cpu()
 
 
 def first_difference(got, want, img):
@@ -130,3 +130,46 @@ def check_fused_equals_two_steps(dev):
                                                                    hb._s()), "ssa_image_u8_crop_flip_normalize")
             assert fused.dtype == hb.ACT_DTYPE and tuple(fused.shape) == (h, w, 16)
             assert torch.equal(fused.view(torch.int16), two.cpu().view(torch.int16)), (window, flip, order)
+
+
+def check_padded_store(dev):
+    """The normalise store at the padded channel counts the Python layer never passes -- 8 (no zero piece) and 24 (two) --
+    through the C ABI, from the plain tail and from the jitter entry (empty program; four operations with the contrast
+    step in the middle): channels 0-2 equal the oracle's tail (on the window; for the jitter entry on the restatement's
+    jittered, mirrored window) cast to the build's element type, the padding is all-zero bits, and the pixel after the
+    last keeps the NaN pattern the buffer was filled with."""
+    import ctypes
+    from oracle.data import crop_flip_normalize as oracle
+    from semseg_amd import _lib, hip_backend as hb
+    from semseg_amd.datasets.transforms import MEAN_STD
+    L = _lib.lib()
+    src = np.random.RandomState(11).randint(0, 256, (12, 16, 3)).astype(np.uint8)
+    H, W = src.shape[:2]
+    window = x0, y0, w, h = (3, 2, 7, 5)
+    nolab = np.zeros((H, W), np.uint8)
+    t = torch.from_numpy(src).to(dev)
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    mean, std = (ctypes.c_float * 3)(*MEAN_STD[0]), (ctypes.c_float * 3)(*MEAN_STD[1])
+    for flip in (False, True):
+        for cpad in (8, 24):
+            for draws in (None, [], draws_of(("brightness", "contrast", "hue", "saturation"))):
+                out = torch.full((h * w + 1, cpad), 0x7FC1, dtype=torch.int16, device=dev)
+                if draws is None:
+                    _lib.check(L.ssa_image_u8_crop_flip_normalize(hb._p(t), H, W, x0, y0, w, h, int(flip), mean, std,
+                                                                  hb._p(out), cpad, hb._s()), "ssa_image_u8_crop_flip_normalize")
+                    want = oracle(src, nolab, window, flip, *MEAN_STD)[0]
+                else:
+                    pg = params(draws).program()
+                    _lib.check(L.ssa_jitter_luma_sum(hb._p(t), H, W, x0, y0, w, h, ctypes.byref(pg), hb._p(counter), hb._s()),
+                               "ssa_jitter_luma_sum")
+                    _lib.check(L.ssa_jitter_crop_flip_normalize(hb._p(t), H, W, x0, y0, w, h, int(flip), ctypes.byref(pg),
+                                                                hb._p(counter), mean, std, hb._p(out), cpad, hb._s()),
+                               "ssa_jitter_crop_flip_normalize")
+                    jittered = R.jitter(src, R.program_of(draws), window, flip)
+                    want = oracle(jittered, nolab, (0, 0, w, h), False, *MEAN_STD)[0]
+                want = torch.from_numpy(want).permute(1, 2, 0).to(hb.ACT_DTYPE).contiguous().view(torch.int16).reshape(h * w, 3)
+                got = out.cpu()
+                case = (flip, cpad, draws)
+                assert torch.equal(got[:h * w, :3], want), case
+                assert int(got[:h * w, 3:].count_nonzero()) == 0, case
+                assert bool((got[h * w] == 0x7FC1).all()), case

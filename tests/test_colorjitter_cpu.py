@@ -166,6 +166,10 @@ def test_emulated_kernels_mean_rounding_windows_and_fused_tail(emu):
     K.check_fused_equals_two_steps(emu)
 
 
+def test_emulated_normalise_store_at_8_and_24_padded_channels(emu):
+    K.check_padded_store(emu)
+
+
 def test_emulated_luma_sum_over_several_workgroups(emu):
     """1 x 257 (a second workgroup with one pixel) and 40 x 64 (ten workgroups, one atomic each)."""
     rng = np.random.RandomState(3)

@@ -146,6 +146,10 @@ def test_fused_tail_equals_jitter_then_tail():
         assert torch.equal(gts, crop_flip_normalize(t, tl, window, flip)[1])
 
 
+def test_normalise_store_at_8_and_24_padded_channels():
+    K.check_padded_store(DEV)
+
+
 def test_fused_tail_on_the_other_storage_build():
     """The same test in a child process on the other build of the library (fp16 storage when this one is bf16)."""
     from semseg_amd import _lib

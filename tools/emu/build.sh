@@ -15,11 +15,13 @@ objs=""
 for f in "$SRC"/*.hip "$HERE/emu_runtime.cpp"; do
   o="$OUT/$(basename "$f" | sed 's/\.[a-z]*$//').o"
   objs="$objs $o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$SRC/common.h" -nt "$o" ] || [ "$SRC/conv_epilogue.h" -nt "$o" ] || [ "$SRC/group.h" -nt "$o" ] || [ "$SRC/jitter_device.h" -nt "$o" ] || \
-     [ "$HERE/include/hip/hip_runtime.h" -nt "$o" ] || [ "$ROOT/include/semseg_hip.h" -nt "$o" ]; then
-    $CXX $FLAGS -c "$f" -o "$o" &
-    pids="$pids $!"
-  fi
+  for d in "$f" "$SRC"/*.h "$HERE/include/hip/hip_runtime.h" "$ROOT/include/semseg_hip.h"; do
+    if [ ! -f "$o" ] || [ "$d" -nt "$o" ]; then
+      $CXX $FLAGS -c "$f" -o "$o" &
+      pids="$pids $!"
+      break
+    fi
+  done
 done
 for p in $pids; do wait "$p"; done
 # Several processes may run this at once (every rank of a multi-process test calls it) while others already have the
