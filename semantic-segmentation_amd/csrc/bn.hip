@@ -57,27 +57,54 @@ __device__ __forceinline__ void block_reduce_2x8(const float* v0, const float* v
 // ssa::kStatReplicas of conv_epilogue.h) replica loads are issued TOGETHER: a rolled loop over a run-time
 // nrep waits for each pair of loads in turn -- eight L2 round trips in the prologue of every workgroup
 // of every apply / backward-apply launch (11-19 us for a TWO-workgroup launch before this).
-__device__ __forceinline__ void replica_sums(const double* __restrict__ sums, int nrep, int C, int c,
-                                             double* s1, double* s2) {
-  double v1[8], v2[8];
+// Two halves, so that a pass can issue the loads, then its data loads, and add up while the data is in flight:
+// replica_issue -- the 16 loads, unconditional (a replica past nrep re-reads replica 0 and is dropped by replica_add);
+// replica_add   -- the sum in replica order (adding +0.0 for r >= nrep changes nothing), replicas from 8 on read here.
+__device__ __forceinline__ void replica_issue(const double* __restrict__ sums, int nrep, int C, int c,
+                                              double (&v1)[8], double (&v2)[8]) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const bool ok = r < nrep;
-    v1[r] = ok ? sums[(long)r * 2 * C + c] : 0.0;
-    v2[r] = ok ? sums[(long)r * 2 * C + C + c] : 0.0;
+    const long ro = (long)(r < nrep ? r : 0) * 2 * C;
+    v1[r] = sums[ro + c];
+    v2[r] = sums[ro + C + c];
   }
+}
+__device__ __forceinline__ void replica_add(const double* __restrict__ sums, int nrep, int C, int c,
+                                            const double (&v1)[8], const double (&v2)[8], double* s1, double* s2) {
   double a = 0.0, b = 0.0;
 #pragma unroll
-  for (int r = 0; r < 8; ++r) { a += v1[r]; b += v2[r]; }      // adding +0.0 for r >= nrep changes nothing
+  for (int r = 0; r < 8; ++r) { a += r < nrep ? v1[r] : 0.0; b += r < nrep ? v2[r] : 0.0; }
   for (int r = 8; r < nrep; ++r) { a += sums[(long)r * 2 * C + c]; b += sums[(long)r * 2 * C + C + c]; }
   *s1 = a;
   *s2 = b;
 }
+__device__ __forceinline__ void replica_sums(const double* __restrict__ sums, int nrep, int C, int c,
+                                             double* s1, double* s2) {
+  double v1[8], v2[8];
+  replica_issue(sums, nrep, C, c, v1, v2);
+  replica_add(sums, nrep, C, c, v1, v2, s1, s2);
+}
+
+// The passes with a coefficient prologue issue the coefficient loads of channel c = t, then the data loads, then the
+// arithmetic.  Vector-memory loads return to a wave in issue order, so the wait in front of the arithmetic is a counted
+// vmcnt(number of data loads), and the fp64 chain, the LDS publish and the barrier run while the data is in flight.
+// issue_order_fence: nothing that touches memory moves across this line, in the compiler's passes or in its instruction
+// scheduler (it emits no instruction and waits for nothing).
+// SSA_PIN_COEF: the loaded values are operands of an empty statement behind the data loads -- the compiler puts its
+// wait for them there, which is that counted wait, and cannot start the arithmetic earlier: left alone it folds the
+// first steps into the block of the coefficient loads and waits for them there, in front of the data loads.
+__device__ __forceinline__ void issue_order_fence() { asm volatile("" ::: "memory"); }
+#ifdef SSA_EMU
+#define SSA_PIN_COEF(q1, q2, ...) issue_order_fence()
+#else
+#define SSA_PIN8(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])
+#define SSA_PIN_COEF(q1, q2, ...) asm volatile("" : SSA_PIN8(q1), SSA_PIN8(q2), __VA_ARGS__ : : "memory")
+#endif
 
 // ---- the streaming passes -------------------------------------------------------------------------------------
 // Every pass gives a thread ROWS pixel rows of its channel group and issues ALL of their loads (up to 3 tensors x
-// ROWS x 16 bytes) before anything else -- also before the per-workgroup coefficient prologue, whose own (L2) loads
-// then fly together with the data: one memory round trip per workgroup instead of the three of round 3 (prologue,
+// ROWS x 16 bytes) together, and before the arithmetic of the per-workgroup coefficient prologue, whose own (L2) loads
+// go out just ahead of them: one memory round trip per workgroup instead of the three of round 3 (prologue,
 // then two batches of four rows behind `#pragma unroll 4`).  Rows past the end of the workgroup's range load the
 // range's first pixel (always valid) and are masked, so the loads are unconditional and issue back to back.  A level
 // of the trunk (7.4 M elements) is in flight in its entirety.
@@ -251,7 +278,8 @@ __device__ __forceinline__ void bn_apply_body(
 }
 
 // Training-mode apply with the finalize step fused in: thread c derives scale/shift of channel c from the fp64
-// sums (the replica loads of all channels issue together, BEHIND the workgroup's data loads), block 0 additionally
+// sums (the replica loads of channel c = t issue AHEAD of the workgroup's data loads, the arithmetic runs under them;
+// the further trips of C > 256 load behind the data as before and drain it), block 0 additionally
 // publishes mean/invstd/scale/shift for the backward pass, updates the running statistics and bumps
 // num_batches_tracked.
 template <int ROWS>
@@ -270,47 +298,79 @@ __device__ __forceinline__ void bn_apply_train_body(
   const int cg = active ? t % VC : 0, pr = active ? t / VC : 0;
   const long pb = bx * pix_per_block;
   const long pe = min(P, pb + pix_per_block);
-  // ---- the first chunk's loads, then the coefficient prologue while they are in flight
+  // ---- the coefficient inputs of channel c = t first, the first chunk's data loads behind them, then the arithmetic:
+  // the replica sums come back ahead of the data and the prologue runs under the data's latency (issue_order_fence)
   RowSet<ROWS> rs;
   rs.init(pb, pe, pr, RP, active);
   uint4 v[ROWS], rv[ROWS];
-  rs.load(x + pb * ldx + cg * 8, ldx, v);
-  if (res) rs.load(res + pb * ldr + cg * 8, ldr, rv);
-  for (int c = t; c < C; c += NT) {
-    double s1 = 0.0, s2 = 0.0;
-    replica_sums(sums, nrep, C, c, &s1, &s2);
+  // scale / shift of a channel from its sums
+  struct Coef { double mean, var, invstd; float sc, sf; };
+  auto derive = [&](double s1, double s2, double g, double b) __attribute__((always_inline)) {
     // This prologue sits on the critical path of EVERY workgroup (the launch is one round of ~900 workgroups: its
     // duration is a workgroup's lifetime), so it holds no fp64 division or square root -- software sequences of a few
     // hundred dependent instructions each: the same pass with the coefficients given ran 6.5 us against 12.8 with them
     // (tools/bnbench.py, profiles/r06_notes.md).  1 / count and count / (count - 1) come from the host;
     // 1 / sqrt(var + eps) is v_rsq_f32 plus one Newton step (the result is stored as fp32 anyway: <= 1 ulp of it).
-    const double mean = s1 * inv_count;
-    double var = s2 * inv_count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float ve = (float)(var + (double)eps);
+    Coef k;
+    k.mean = s1 * inv_count;
+    k.var = s2 * inv_count - k.mean * k.mean;
+    if (k.var < 0.0) k.var = 0.0;
+    const float ve = (float)(k.var + (double)eps);
     float rs = ssa_rsqrt(ve);
     rs = rs * (1.5f - 0.5f * ve * rs * rs);
-    const double invstd = (double)rs;
-    const double g = gamma ? (double)gamma[c] : 1.0;
-    const double b = beta ? (double)beta[c] : 0.0;
-    const float sc = (float)(g * invstd), sf = (float)(b - mean * g * invstd);
-    sh[c] = sc;
-    sh[C + c] = sf;
+    k.invstd = (double)rs;
+    k.sc = (float)(g * k.invstd);
+    k.sf = (float)(b - k.mean * g * k.invstd);
+    return k;
+  };
+  // the table of this launch in LDS; block 0 publishes it and updates the running statistics
+  auto publish = [&](int c, const Coef& k) __attribute__((always_inline)) {
+    sh[c] = k.sc;
+    sh[C + c] = k.sf;
     if (bx == 0) {
-      coef[c] = sc;
-      coef[C + c] = sf;
-      coef[2 * C + c] = (float)mean;
-      coef[3 * C + c] = (float)invstd;
+      coef[c] = k.sc;
+      coef[C + c] = k.sf;
+      coef[2 * C + c] = (float)k.mean;
+      coef[3 * C + c] = (float)k.invstd;
       if (running_mean) {
-        const double unbiased = var * unbias;
-        running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
+        const double unbiased = k.var * unbias;
+        running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * k.mean);
         running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
       }
       if (pass_stats) {
-        pass_stats[c] = (float)mean;
-        pass_stats[C + c] = (float)var;
+        pass_stats[c] = (float)k.mean;
+        pass_stats[C + c] = (float)k.var;
       }
     }
+  };
+  // all the loads are unconditional -- a load behind a test of its pointer is waited for on the spot -- so a null
+  // gamma / beta reads a word of the sums instead, which the select at the use drops
+  const bool first = t < C;
+  double q1[8], q2[8];
+  float g0 = 0.f, b0 = 0.f;
+  if (first) {
+    replica_issue(sums, nrep, C, t, q1, q2);
+    g0 = *(gamma ? gamma + t : reinterpret_cast<const float*>(sums));
+    b0 = *(beta ? beta + t : reinterpret_cast<const float*>(sums));
+  }
+  issue_order_fence();
+  // The same number of data loads with and without a residual, so that ONE wait is right for both (a wait behind the
+  // join of two branches is counted for the shorter one, i.e. waits for the first rows of x on the layers with a residual;
+  // two copies of the pass in one kernel each wait for the other's loads, whose registers they re-use): without a
+  // residual the rows of rv all read the first 16 bytes of the workgroup's x range (aligned like every load of x; one
+  // cache line per wave, which the x loads fetch anyway), dropped by bn_apply_rows.
+  rs.load(x + pb * ldx + cg * 8, ldx, v);
+  rs.load(res ? res + pb * ldr + cg * 8 : x + pb * ldx, res ? ldr : 0, rv);
+  SSA_PIN_COEF(q1, q2, "+v"(g0), "+v"(b0));
+  if (first) {
+    double s1 = 0.0, s2 = 0.0;
+    replica_add(sums, nrep, C, t, q1, q2, &s1, &s2);
+    publish(t, derive(s1, s2, gamma ? (double)g0 : 1.0, beta ? (double)b0 : 0.0));
+  }
+  for (int c = t + NT; c < C; c += NT) {      // wider layers: the further trips behind the data, as before
+    double s1 = 0.0, s2 = 0.0;
+    replica_sums(sums, nrep, C, c, &s1, &s2);
+    publish(c, derive(s1, s2, gamma ? (double)gamma[c] : 1.0, beta ? (double)beta[c] : 0.0));
   }
   if (bx == 0 && t == 0) {
     if (num_batches_tracked) *num_batches_tracked += 1;
@@ -368,9 +428,10 @@ __device__ __forceinline__ void load_sign_bytes(const RowSet<ROWS>& rs, const un
 
 // MODE as in bn_bwd_apply_body below (0: sign bytes / no ReLU, 1: mask recomputed from x, 2: mask read off z).  The loop
 // accumulates sum g and sum g x per thread and centres ONCE at the end -- sum g xhat = invstd (sum g x - mean sum g), per
-// thread, over its <= ROWS x chunks pixels, before the block reduction -- so mean / invstd are not live in it: with the
-// mask source compile-time and the rows kept apart the 8-row form fits 128 registers (it ran at 246 = two workgroups per
-// CU: a head-sized launch of 1,280-3,072 workgroups took three to six rounds).
+// thread, over its <= ROWS x chunks pixels, before the block reduction -- so mean / invstd need not be live in it: with
+// the mask source compile-time and the rows kept apart the 4-row forms fit 128 registers (98-128) and the 8-row forms,
+// the default, run at 148-202 (they ran at 246); the 8-row forms that can afford it hold mean / invstd through the loop
+// (EARLY below; registers per instantiation in profiles/bn_prologue_resources.txt).
 template <int ROWS, int MODE>
 __device__ __forceinline__ void bn_bwd_reduce_body(
     const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ dz, int lddz,
@@ -391,6 +452,17 @@ __device__ __forceinline__ void bn_bwd_reduce_body(
   for (int j = 0; j < 8; ++j) { sg[j] = 0.f; sgx[j] = 0.f; ma[j] = 0.f; mb[j] = 0.f; }
   const long pb = bx * pix_per_block;
   const long pe = min(P, pb + pix_per_block);
+  // mean / invstd are wanted behind the loop only; loaded there they are one more L2 round trip between the last row and
+  // the block reduction.  The 8-row form (the default: 256 registers to spend) fetches them ahead of the first data loads;
+  // the 2- and 4-row forms have no 16 registers to hold them through the loop, and the 8-row form that reads z would go
+  // from three waves per SIMD to two (154 -> 170 registers).
+  constexpr bool EARLY = ROWS > 4 && !ZMASK;
+  float mu[8], is[8];
+  if constexpr (EARLY) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { mu[j] = mean[cg * 8 + j]; is[j] = invstd[cg * 8 + j]; }
+    issue_order_fence();
+  }
   for (long p0 = pb; p0 < pe; p0 += (long)RP * ROWS) {
     RowSet<ROWS> rs;
     rs.init(p0, pe, pr, RP, active);
@@ -424,8 +496,12 @@ __device__ __forceinline__ void bn_bwd_reduce_body(
 #endif
     }
   }
+  if constexpr (!EARLY) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) sgx[j] = (sgx[j] - mean[cg * 8 + j] * sg[j]) * invstd[cg * 8 + j];
+    for (int j = 0; j < 8; ++j) { mu[j] = mean[cg * 8 + j]; is[j] = invstd[cg * 8 + j]; }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) sgx[j] = (sgx[j] - mu[j] * sg[j]) * is[j];
   block_reduce_2x8(sg, sgx, cg, C, active, sums, sh, bx, nrep);
 }
 
@@ -456,27 +532,22 @@ __device__ __forceinline__ void bn_bwd_apply_body(
   const bool from_x = MODE == 1 && relu;
   const long pb = bx * pix_per_block;
   const long pe = min(P, pb + pix_per_block);
-  // ---- the first chunk's loads, then the coefficient prologue while they are in flight
+  // ---- the coefficient inputs of channel c = t first, the first chunk's data loads behind them, then the arithmetic
+  // (see the training apply and issue_order_fence)
   RowSet<ROWS> rs;
   rs.init(pb, pe, pr, RP, active);
   uint4 gv[ROWS], xr[ROWS], zr[ZMASK ? ROWS : 1];
   unsigned mk[MODE == 0 ? ROWS : 1];
-  rs.load(dz + pb * lddz + cg * 8, lddz, gv);
-  rs.load(x + pb * ldx + cg * 8, ldx, xr);
-  if constexpr (ZMASK) rs.load(z + pb * ldz + cg * 8, ldz, zr);
-  if constexpr (MODE == 0) { if (use_bits) load_sign_bytes<ROWS>(rs, mask + pb * VC + cg, VC, mk); }
-  for (int c = t; c < C; c += NT) {
-    double s1 = 0.0, s2 = 0.0;
-    replica_sums(sums, nrep, C, c, &s1, &s2);
-    const float is_ = invstd[c], mu_ = mean[c];
-    const float a_ = (gamma ? gamma[c] : 1.f) * is_;
+  auto finish = [&](int c, double s1, double s2, float is_, float mu_, float gam, float msc, float msh)
+                    __attribute__((always_inline)) {
+    const float a_ = gam * is_;
     const float c1_ = (float)(s1 * inv_count);    // (no fp64 division on every workgroup's critical path: see the apply)
     const float c2_ = (float)(s2 * inv_count);
     sh[c] = a_;
     sh[C + c] = -a_ * c2_ * is_;
     sh[2 * C + c] = a_ * (c2_ * is_ * mu_ - c1_);
-    sh[3 * C + c] = mscale ? mscale[c] : 0.f;
-    sh[4 * C + c] = mscale ? mshift[c] : 0.f;
+    sh[3 * C + c] = msc;
+    sh[4 * C + c] = msh;
     if (bx == 0) {
       // accumulate_pg: the gradient buffer is shared by every pass over this layer (cleared once
       // per step); passes grouped into one launch add concurrently, hence the atomics
@@ -488,6 +559,40 @@ __device__ __forceinline__ void bn_bwd_apply_body(
         if (dgamma) dgamma[c] = (float)(s2 * param_grad_scale);
       }
     }
+  };
+  const bool first = t < C;
+  const bool ms_on = MODE == 1 && mscale != nullptr;
+  double q1[8], q2[8];
+  float is0 = 0.f, mu0 = 0.f, g0 = 0.f, ms0 = 0.f, mh0 = 0.f;
+  if (first) {            // (unconditional loads, as in the training apply)
+    replica_issue(sums, nrep, C, t, q1, q2);
+    is0 = invstd[t];
+    mu0 = mean[t];
+    g0 = *(gamma ? gamma + t : reinterpret_cast<const float*>(sums));
+    if constexpr (MODE == 1) {
+      ms0 = *(ms_on ? mscale + t : reinterpret_cast<const float*>(sums));
+      mh0 = *(ms_on ? mshift + t : reinterpret_cast<const float*>(sums));
+    }
+  }
+  issue_order_fence();
+  rs.load(dz + pb * lddz + cg * 8, lddz, gv);
+  rs.load(x + pb * ldx + cg * 8, ldx, xr);
+  if constexpr (ZMASK) rs.load(z + pb * ldz + cg * 8, ldz, zr);
+  // (MODE 0: the same number of loads with and without the sign bytes -- see the training apply; without them every row
+  // reads the first byte of the workgroup's x range)
+  if constexpr (MODE == 0)
+    load_sign_bytes<ROWS>(rs, use_bits ? mask + pb * VC + cg : reinterpret_cast<const unsigned char*>(x + pb * ldx),
+                          use_bits ? VC : 0, mk);
+  SSA_PIN_COEF(q1, q2, "+v"(is0), "+v"(mu0), "+v"(g0), "+v"(ms0), "+v"(mh0));
+  if (first) {
+    double s1 = 0.0, s2 = 0.0;
+    replica_add(sums, nrep, C, t, q1, q2, &s1, &s2);
+    finish(t, s1, s2, is0, mu0, gamma ? g0 : 1.f, ms_on ? ms0 : 0.f, ms_on ? mh0 : 0.f);
+  }
+  for (int c = t + NT; c < C; c += NT) {      // wider layers: the further trips behind the data, as before
+    double s1 = 0.0, s2 = 0.0;
+    replica_sums(sums, nrep, C, c, &s1, &s2);
+    finish(c, s1, s2, invstd[c], mean[c], gamma ? gamma[c] : 1.f, ms_on ? mscale[c] : 0.f, ms_on ? mshift[c] : 0.f);
   }
   __syncthreads();
   if (!active) return;
