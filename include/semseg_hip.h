@@ -397,6 +397,30 @@ int ssa_bn_bwd_apply(const void* x, int ldx, const void* dz, int lddz,
                      long pix_per_img, float* dgamma, float* dbeta,
                      float param_grad_scale, const float* mask_scale,
                      const float* mask_shift, int accumulate_param_grads, const void* sign_mask, void* stream);
+/* ------------------------------------------------- pre-activation blocks ----
+ * IdentityResidualBlock.forward (network/wider_resnet.py:172-185): the block input is a residual SUM, and it feeds
+ * both bn1 and the shortcut (`shortcut = x.clone(); bn1 = self.bn1(x); ...; out.add_(shortcut)`), so the batch
+ * statistics cannot ride on a conv epilogue and the input's gradient is bn1's dx plus the shortcut's.
+ * forward: s[p,c] = round16(float(a) + float(b)) (16-byte pieces; bit for bit ssa_sum_act's), and
+ * sums[0:C] += sum_p s, sums[C:2C] += sum_p s^2 over the values AS STORED: [1][2][C] fp64, what
+ * ssa_bn_apply_train(..., nrep = 1) and the SyncBN exchange take.  One pass (read 2, write 1) for the sum pass and
+ * the statistics pass (read 2 write 1, read 1).  a, b, s: 16-byte aligned, leading dimensions % 8 and >= C
+ * (channel slices work); C % 8, C <= 2048.  zero_sums as in ssa_bn_stats.                                  */
+int ssa_add_bn_stats(const void* a, int lda, const void* b, int ldb, void* s, int lds, long P,
+                     int C, double* sums, int zero_sums, void* stream);
+/* backward: ssa_bn_bwd_apply with dx = round16((A g + (Bx x + D)) + float(dadd)) -- the shortcut's gradient is a
+ * fourth load stream of the pass and the sum is rounded once, instead of an add pass (read 2, write 1) behind it.
+ * Built for the form that recomputes the ReLU mask from x (relu with mask_scale / mask_shift: the pre-activation
+ * ReLU sits directly behind its BatchNorm); every other form returns SSA_EUNSUPPORTED.                    */
+int ssa_bn_bwd_apply_add(const void* x, int ldx, const void* dz, int lddz,
+                         const void* z, int ldz, void* dx, int lddx, void* dres,
+                         int lddres, long P, int C, const float* gamma,
+                         const float* mean, const float* invstd, const double* sums,
+                         int nrep, double count, int relu, const float* post,
+                         long pix_per_img, float* dgamma, float* dbeta,
+                         float param_grad_scale, const float* mask_scale,
+                         const float* mask_shift, int accumulate_param_grads, const void* sign_mask,
+                         const void* dadd, int lddadd, void* stream);
 /* dgamma[c] = sums[C+c], dbeta[c] = sums[c] (fp64 -> fp32)                     */
 int ssa_bn_param_grads(const double* sums, int C, float* dgamma, float* dbeta,
                        void* stream);

@@ -159,6 +159,50 @@ __device__ __forceinline__ void bn_stats_body(const bf16_t* __restrict__ x, long
   block_reduce_2x8(s, q, cg, C, active, sums, sh, bx);
 }
 
+// Head of a pre-activation block (network/wider_resnet.py:172-185): the residual sum s = a + b is stored ONCE, rounded to
+// 16 bits, and the batch statistics of the BatchNorm that follows are taken from the values as stored, in the same pass --
+// where the sum, the statistics and the apply were three passes (read 2 write 1, read 1, read 1 write 1), the first two
+// are one (read 2 write 1).  Thread mapping, masking and block reduction of bn_stats_body; the loads of BOTH operands
+// (2 x ROWS x 16 bytes) are issued together.
+template <int ROWS>
+__device__ __forceinline__ void add_bn_stats_body(const bf16_t* __restrict__ a, int lda, const bf16_t* __restrict__ b,
+                                                  int ldb, bf16_t* __restrict__ s, int lds, long P, int C,
+                                                  double* __restrict__ sums, long pix_per_block, const int bx) {
+  SSA_DYN_LDS(float, sh);
+  const int VC = C >> 3, NA = active_threads(VC), RP = NA / VC;
+  const int t = threadIdx.x;
+  const bool active = t < NA;
+  const int cg = active ? t % VC : 0, pr = active ? t / VC : 0;
+  float s1[8], s2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+  const long pb = bx * pix_per_block;
+  const long pe = min(P, pb + pix_per_block);
+  for (long p0 = pb; p0 < pe; p0 += (long)RP * ROWS) {
+    RowSet<ROWS> rs;
+    rs.init(p0, pe, pr, RP, active);
+    uint4 va[ROWS], vb[ROWS];
+    rs.load(a + p0 * lda + cg * 8, lda, va);
+    rs.load(b + p0 * ldb + cg * 8, ldb, vb);
+#pragma unroll
+    for (int u = 0; u < ROWS; ++u) {
+      const bool ok = (rs.ok >> u) & 1u;
+      float f[8], g[8];
+      unpack8(va[u], f);
+      unpack8(vb[u], g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] += g[j];
+      const uint4 pk = pack8(f);
+      if (ok) *reinterpret_cast<uint4*>(s + (p0 + rs.off[u]) * lds + cg * 8) = pk;
+      unpack8(pk, f);                                   // the statistics are those of the STORED sum
+      const float keep = ok ? 1.f : 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float fk = f[j] * keep; s1[j] += fk; s2[j] += fk * f[j]; }
+    }
+  }
+  block_reduce_2x8(s1, s2, cg, C, active, sums, sh, bx);
+}
+
 __global__ void bn_finalize_kernel(const double* __restrict__ sums, double count, int C,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                    float* __restrict__ running_mean, float* __restrict__ running_var,
@@ -507,7 +551,10 @@ __device__ __forceinline__ void bn_bwd_reduce_body(
 
 // MODE: where the ReLU mask comes from -- 0: the forward's sign bytes (or there is no ReLU), 1: recomputed from x
 // (mask scale / shift), 2: read off z.  Compile-time, so that each form holds only its own operands in registers.
-template <int ROWS, int MODE>
+// ADD (pre-activation blocks): the block input feeds this BatchNorm AND the shortcut, so its gradient is the BatchNorm's
+// dx plus the gradient `dadd` that arrives over the shortcut -- a fourth load stream issued with the others and one
+// rounding of the sum, instead of a separate add pass (read 2, write 1) behind this one.
+template <int ROWS, int MODE, bool ADD = false>
 __device__ __forceinline__ void bn_bwd_apply_body(
     const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ dz, int lddz,
     const bf16_t* __restrict__ z, int ldz, bf16_t* __restrict__ dx, int lddx,
@@ -517,7 +564,7 @@ __device__ __forceinline__ void bn_bwd_apply_body(
     const float* __restrict__ post, long pix_per_img, long pix_per_block,
     float* __restrict__ dgamma, float* __restrict__ dbeta, float param_grad_scale,
     const float* __restrict__ mscale, const float* __restrict__ mshift, const int accumulate_pg,
-    const unsigned char* __restrict__ mask, const int bx) {
+    const unsigned char* __restrict__ mask, const int bx, const bf16_t* __restrict__ dadd = nullptr, int lddadd = 0) {
   // dx = a (g - c1 - xhat c2),  xhat = (x - mean) invstd,  a = gamma invstd,  c1 = sum_g / N,  c2 = sum_g_xhat / N
   //    = A g + (Bx x + D)   with   A = a,  Bx = -a c2 invstd,  D = a (c2 invstd mean - c1):
   // three per-channel constants in registers instead of five (this pass ran at 173 registers = TWO workgroups per CU;
@@ -536,7 +583,7 @@ __device__ __forceinline__ void bn_bwd_apply_body(
   // (see the training apply and issue_order_fence)
   RowSet<ROWS> rs;
   rs.init(pb, pe, pr, RP, active);
-  uint4 gv[ROWS], xr[ROWS], zr[ZMASK ? ROWS : 1];
+  uint4 gv[ROWS], xr[ROWS], zr[ZMASK ? ROWS : 1], av[ADD ? ROWS : 1];
   unsigned mk[MODE == 0 ? ROWS : 1];
   auto finish = [&](int c, double s1, double s2, float is_, float mu_, float gam, float msc, float msh)
                     __attribute__((always_inline)) {
@@ -578,6 +625,7 @@ __device__ __forceinline__ void bn_bwd_apply_body(
   rs.load(dz + pb * lddz + cg * 8, lddz, gv);
   rs.load(x + pb * ldx + cg * 8, ldx, xr);
   if constexpr (ZMASK) rs.load(z + pb * ldz + cg * 8, ldz, zr);
+  if constexpr (ADD) rs.load(dadd + pb * lddadd + cg * 8, lddadd, av);
   // (MODE 0: the same number of loads with and without the sign bytes -- see the training apply; without them every row
   // reads the first byte of the workgroup's x range)
   if constexpr (MODE == 0)
@@ -623,6 +671,12 @@ __device__ __forceinline__ void bn_bwd_apply_body(
       float o[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = A[j] * g[j] + (Bx[j] * xv[j] + D[j]);
+      if constexpr (ADD) {
+        float ad[8];
+        unpack8(av[u], ad);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] += ad[j];
+      }
       if (ok) *reinterpret_cast<uint4*>(dx + (p0 + rs.off[u]) * lddx + cg * 8) = pack8(o);
 #ifndef SSA_EMU
       __builtin_amdgcn_sched_barrier(0);        // one row at a time (register pressure: see bn_apply_rows)
@@ -634,6 +688,7 @@ __device__ __forceinline__ void bn_bwd_apply_body(
     rs.load(dz + p0 * lddz + cg * 8, lddz, gv);
     rs.load(x + p0 * ldx + cg * 8, ldx, xr);
     if constexpr (ZMASK) rs.load(z + p0 * ldz + cg * 8, ldz, zr);
+    if constexpr (ADD) rs.load(dadd + p0 * lddadd + cg * 8, lddadd, av);
     if constexpr (MODE == 0) { if (use_bits) load_sign_bytes<ROWS>(rs, mask + p0 * VC + cg, VC, mk); }
   }
 }
@@ -655,6 +710,14 @@ struct BnStatsK {
   static constexpr int NT = ::NT;
   static __device__ __forceinline__ void run(const Args& a, int bx, int, int) {
     bn_stats_body<ROWS>(a.x, a.P, a.C, a.ld, a.sums, a.ppb, bx, true);
+  }
+};
+template <int ROWS>
+struct AddBnStatsK {
+  struct Args { const bf16_t* a; const bf16_t* b; bf16_t* s; double* sums; long P, ppb; int C, lda, ldb, lds; };
+  static constexpr int NT = ::NT;
+  static __device__ __forceinline__ void run(const Args& a, int bx, int, int) {
+    add_bn_stats_body<ROWS>(a.a, a.lda, a.b, a.ldb, a.s, a.lds, a.P, a.C, a.sums, a.ppb, bx);
   }
 };
 template <int ROWS>
@@ -725,6 +788,22 @@ struct BnBwdApplyKM {
 template <int ROWS> struct BnBwdApplyK : BnBwdApplyKM<ROWS, 0> {};
 template <int ROWS> struct BnBwdApplyXK : BnBwdApplyKM<ROWS, 1> {};
 template <int ROWS> struct BnBwdApplyZK : BnBwdApplyKM<ROWS, 2> {};
+// the mask-from-x form with the shortcut's gradient added (bn1 of a pre-activation block; bn_bwd_apply_body's ADD)
+template <int ROWS>
+struct BnBwdApplyAddXK {
+  // the fourth stream is 4 more registers per row in flight: the 4-row form (125 registers without it) needs 141 and
+  // spills 68 bytes when held to 128 -- three workgroups per CU instead of four, and no scratch
+  static constexpr int WPE = ROWS <= 4 ? 3 : 2;
+  struct Args { typename BnBwdApplyKM<ROWS, 1>::Args k; const bf16_t* dadd; int lddadd; };
+  static constexpr int NT = ::NT;
+  static __device__ __forceinline__ void run(const Args& b, int bx, int, int) {
+    const typename BnBwdApplyKM<ROWS, 1>::Args& a = b.k;
+    bn_bwd_apply_body<ROWS, 1, true>(a.x, a.ldx, a.dz, a.lddz, a.z, a.ldz, a.dx, a.lddx, a.dres, a.lddres, a.P, a.C,
+                                     a.gamma, a.mean, a.invstd, a.sums, a.nrep, a.inv_count, a.relu, a.post, a.pix_per_img,
+                                     a.ppb, a.dgamma, a.dbeta, a.param_grad_scale, a.mscale, a.mshift, a.accumulate_pg, a.mask,
+                                     bx, b.dadd, b.lddadd);
+  }
+};
 
 
 __global__ void d2f_kernel(const double* __restrict__ in, float* __restrict__ out, int n) {
@@ -854,6 +933,20 @@ int ssa_bn_stats(const void* x, long P, int C, int ld, double* sums, int zero_su
   return SSA_BN_SUBMIT(BnStatsK, g, ({(const bf16_t*)x, sums, P, g.ppb, C, ld}), 16 * (NT + 1) * sizeof(float), s);
 }
 
+int ssa_add_bn_stats(const void* a, int lda, const void* b, int ldb, void* s, int lds, long P, int C, double* sums,
+                     int zero_sums, void* stream) {
+  if (!a || !b || !s || !sums || !ok_c(C) || !ok_p(P) || lda % 8 || ldb % 8 || lds % 8) return SSA_EINVAL;
+  if (lda < C || ldb < C || lds < C || ((uintptr_t)a | (uintptr_t)b | (uintptr_t)s) % 16) return SSA_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (zero_sums) {
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  const Grid g = plan_reduce_grid(P, C);
+  return SSA_BN_SUBMIT(AddBnStatsK, g, ({(const bf16_t*)a, (const bf16_t*)b, (bf16_t*)s, sums, P, g.ppb, C, lda, ldb, lds}),
+                       16 * (NT + 1) * sizeof(float), st);
+}
+
 int ssa_bn_finalize(const double* sums, double count, int C, const float* gamma, const float* beta,
                     float* running_mean, float* running_var, float momentum, float eps,
                     int use_running, float* scale, float* shift, float* mean, float* invstd,
@@ -961,6 +1054,27 @@ int ssa_bn_bwd_apply(const void* x, int ldx, const void* dz, int lddz, const voi
   if (relu && !sign_mask) return SSA_BN_BWD_APPLY(BnBwdApplyZK);
   return SSA_BN_BWD_APPLY(BnBwdApplyK);
 #undef SSA_BN_BWD_APPLY
+}
+
+int ssa_bn_bwd_apply_add(const void* x, int ldx, const void* dz, int lddz, const void* z, int ldz,
+                         void* dx, int lddx, void* dres, int lddres, long P, int C, const float* gamma,
+                         const float* mean, const float* invstd, const double* sums, int nrep,
+                         double count, int relu, const float* post, long pix_per_img, float* dgamma,
+                         float* dbeta, float param_grad_scale, const float* mask_scale,
+                         const float* mask_shift, int accumulate_param_grads, const void* sign_mask,
+                         const void* dadd, int lddadd, void* stream) {
+  if (!x || !dz || !dx || !dadd || !sums || !mean || !invstd || !ok_c(C) || !ok_p(P) || nrep < 1 || count <= 0 ||
+      (mask_scale && !mask_shift))
+    return SSA_EINVAL;
+  if (ldx % 8 || lddz % 8 || lddx % 8 || lddadd % 8 || (dres && lddres % 8)) return SSA_EINVAL;
+  // the pre-activation ReLU sits directly behind its BatchNorm: only the form that recomputes the mask from x is built
+  if (!relu || !mask_scale) return SSA_EUNSUPPORTED;
+  const Grid g = plan_grid(P, C, bwd_rows(), 16384, prologue_chunks(C));
+  return SSA_BN_SUBMIT(BnBwdApplyAddXK, g,
+                       ({{(const bf16_t*)x, (const bf16_t*)dz, (const bf16_t*)z, (bf16_t*)dx, (bf16_t*)dres, gamma, mean, invstd,
+                          sums, post, dgamma, dbeta, mask_scale, mask_shift, (const unsigned char*)sign_mask, 1.0 / count, P,
+                          pix_per_img, g.ppb, ldx, lddz, ldz, lddx, lddres, C, nrep, relu, param_grad_scale,
+                          accumulate_param_grads}, (const bf16_t*)dadd, lddadd}), 5 * C * sizeof(float), (hipStream_t)stream);
 }
 
 int ssa_bn_param_grads(const double* sums, int C, float* dgamma, float* dbeta, void* stream) {

@@ -140,6 +140,10 @@ _SIGS = {
                            c_long, _P, c_int, c_int, _P, _P, _P, _P], c_int),
     "ssa_bn_bwd_apply": ([_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_long, c_int,
                           _P, _P, _P, _P, c_int, c_double, c_int, _P, c_long, _P, _P, c_float, _P, _P, c_int, _P, _P], c_int),
+    "ssa_add_bn_stats": ([_P, c_int, _P, c_int, _P, c_int, c_long, c_int, _P, c_int, _P], c_int),
+    "ssa_bn_bwd_apply_add": ([_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_long, c_int,
+                              _P, _P, _P, _P, c_int, c_double, c_int, _P, c_long, _P, _P, c_float, _P, _P, c_int, _P,
+                              _P, c_int, _P], c_int),
     "ssa_bn_param_grads": ([_P, c_int, _P, _P, _P], c_int),
     "ssa_p2p_buffer_bytes": ([c_int, c_long, POINTER(c_size_t)], c_int),
     "ssa_p2p_allreduce_f64": ([_P, c_long, _P, c_int, c_int, _P, c_long, _P], c_int),

@@ -1428,11 +1428,16 @@ def _bn_bwd(jobs):
             dx = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev)
             dres = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev) if j["has_res"] else None
             _note(0.0, 2.0 * P * C * (3 + (1 if dres is not None else 0)))
-            check(L.ssa_bn_bwd_apply(_p(x), j["ldx"], _p(j["dz"]), j["lddz"], _p(j["z"]), C, _p(dx), C, _p(dres), C, P, C,
-                                     _p(g), _p(coef[2]), _p(coef[3]), _p(use_sums), j["nrep"], j["count"], int(j["relu"]),
-                                     _p(j["pst"]), H * W, _p(pg_g) if fuse_pg else None, _p(pg_b) if fuse_pg else None,
-                                     pscale, _p(msc), _p(msh), accumulate if fuse_pg else 0, _p(j.get("mask")), _s()),
-                  "ssa_bn_bwd_apply")
+            args = (_p(x), j["ldx"], _p(j["dz"]), j["lddz"], _p(j["z"]), C, _p(dx), C, _p(dres), C, P, C,
+                    _p(g), _p(coef[2]), _p(coef[3]), _p(use_sums), j["nrep"], j["count"], int(j["relu"]),
+                    _p(j["pst"]), H * W, _p(pg_g) if fuse_pg else None, _p(pg_b) if fuse_pg else None,
+                    pscale, _p(msc), _p(msh), accumulate if fuse_pg else 0, _p(j.get("mask")))
+            if j.get("dadd") is not None:
+                # head of a pre-activation block: the gradient over the shortcut joins dx inside the pass (AddBnActFn)
+                _note(0.0, 2.0 * P * C)
+                check(L.ssa_bn_bwd_apply_add(*args, _p(j["dadd"]), j["lddadd"], _s()), "ssa_bn_bwd_apply_add")
+            else:
+                check(L.ssa_bn_bwd_apply(*args, _s()), "ssa_bn_bwd_apply")
             out.append((dx, dres, ret_g, ret_b))
     for sums, C, tmp, pg_g, pg_b in tails:
         if tmp is None:
@@ -1608,6 +1613,55 @@ class BnActGroupFn(torch.autograd.Function):
             grads[3 + 5 * i] = db
             grads[4 + 5 * i] = dres
         return tuple(grads)
+
+
+class AddBnActFn(torch.autograd.Function):
+    """Head of a pre-activation block (network/wider_resnet.py:172-185), training mode: s = a + b and
+    z = post * relu(bn(s)) -- (s, z).  Forward: ssa_add_bn_stats (the sum stored once, its batch statistics taken in the
+    same pass), then ssa_bn_apply_train.  Backward: ssa_bn_bwd_reduce, then ssa_bn_bwd_apply_add with the gradient that
+    arrives at s (the shortcut's) as the fourth stream -- or the plain ssa_bn_bwd_apply when s has no other consumer.
+    The ReLU mask is recomputed from s with the forward's scale / shift: z is not kept."""
+
+    @staticmethod
+    def forward(ctx, meta, a, b, gamma, beta, post):
+        ctx.set_materialize_grads(False)
+        assert meta.training and meta.relu
+        a, lda = _pixels(a)
+        b, ldb = _pixels(b)
+        if a.data_ptr() % 16 or lda % 8:
+            a, lda = a.contiguous(), a.shape[3]
+        if b.data_ptr() % 16 or ldb % 8:
+            b, ldb = b.contiguous(), b.shape[3]
+        B, H, W, C = a.shape
+        P = B * H * W
+        s = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=a.device)
+        sums = _ARENA.take(2 * C, a.device)
+        _note(0.0, 2.0 * P * C * 3)
+        check(lib().ssa_add_bn_stats(_p(a), lda, _p(b), ldb, _p(s), C, P, C, _p(sums), 0, _s()), "ssa_add_bn_stats")
+        _PENDING_STATS[s.data_ptr()] = (sums, 1)        # picked up (and, under SyncBN, exchanged) by _bn_train_fwd
+        g = gamma.detach().float() if gamma is not None else None
+        bt = beta.detach().float() if beta is not None else None
+        pst = post.float().contiguous() if post is not None else None
+        zs, coefs, counts, worlds = _bn_train_fwd([s], [C], [meta], [g], [bt], [None], [pst])
+        ctx.save_for_backward(s, g, coefs[0], pst)
+        ctx.info = (worlds[0], counts[0])
+        ctx.params = (gamma, beta)
+        return s, zs[0]
+
+    @staticmethod
+    def backward(ctx, ds, dz):
+        s, g, coef, pst = ctx.saved_tensors
+        C = s.shape[3]
+        if dz is None:
+            return None, ds, ds, None, None, None
+        dz, lddz = _dz_bf16(dz, C)
+        job = dict(x=s, ldx=C, dz=dz, lddz=lddz, z=None, mask=None, coef=coef, g=g, gamma_param=ctx.params[0],
+                   beta_param=ctx.params[1], relu=True, pst=pst, training=True, world=ctx.info[0], count=ctx.info[1],
+                   has_res=False, mask_from_x=True, sums=None)
+        if ds is not None:
+            job["dadd"], job["lddadd"] = _dz_bf16(ds, C)
+        dx, _, dg, db = _bn_bwd([job])[0]
+        return None, dx, dx, dg, db, None
 
 
 class BatchNormActFn:

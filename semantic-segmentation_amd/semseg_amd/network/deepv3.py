@@ -1,6 +1,8 @@
 """DeepLabV3+ (network/deepv3.py:44-93 of the reference) with the ResNet-50 trunk:
 the `--arch deepv3.DeepV3PlusR50` of BASELINE.json configs[0].  Same factory
-name, call contract and state_dict (363 keys); NHWC bf16 on the HIP kernels."""
+name, call contract and state_dict (363 keys); NHWC bf16 on the HIP kernels.
+`DeepV3PlusW38` / `DeepV3PlusW38I` (network/deepv3.py:108-114): the same head on
+the WiderResNet-38 trunk of scripts/train_cityscapes_deepv3.yml."""
 import torch
 from torch import nn
 
@@ -93,3 +95,11 @@ class DeepV3Plus(nn.Module):
 
 def DeepV3PlusR50(num_classes, criterion):
     return DeepV3Plus(num_classes, trunk="resnet-50", criterion=criterion)
+
+
+def DeepV3PlusW38(num_classes, criterion):
+    return DeepV3Plus(num_classes, trunk="wrn38", criterion=criterion)
+
+
+def DeepV3PlusW38I(num_classes, criterion):
+    return DeepV3Plus(num_classes, trunk="wrn38", criterion=criterion, init_all=True)

@@ -64,6 +64,13 @@ class BackendBase:
         return [self._batch_norm_act(xi, b, r, rl, po) for xi, b, r, rl, po in
                 zip(x, _lst(bn, n), _lst(residual, n), _lst(relu, n), _lst(post, n))]
 
+    def add_bn_act(self, a, b, bn, relu=True, post=None):
+        """Head of a pre-activation block (network/wider_resnet.py:172-185): s = a + b, z = post * act(bn(s)); returns
+        (s, z).  s is the block input: it also feeds the shortcut.  Here the composition of the two ops; the HIP backend
+        takes the batch statistics in the pass that stores the sum and adds the shortcut's gradient in bn's backward."""
+        s = self.sum_act([a, b], relu=False)
+        return s, self.batch_norm_act(s, bn, None, relu, post)
+
     def basic_block(self, blocks, xs):
         """conv3x3-BN-ReLU-conv3x3-BN-(+x)-ReLU (network/hrnetv2.py:37-66, no downsample branch)
         of blocks[i] on xs[i]."""
@@ -220,6 +227,13 @@ class HipBackend(BackendBase):
             flat += [xi, c.weight, c.bias]
         ys = self.hb.ConvGroupFn.apply(spec, *flat)
         return self._bn_group(list(ys), bns, ress, relus, posts, outs)
+
+    def add_bn_act(self, a, b, bn, relu=True, post=None):
+        C = a.shape[3]
+        if not (bn.training and relu and a.dtype == self.act_dtype and b.dtype == self.act_dtype and C % 8 == 0 and C <= 2048):
+            # inference (ssa_sum_act, then the evaluation apply) and forms the fused passes are not built for
+            return BackendBase.add_bn_act(self, a, b, bn, relu, post)
+        return self.hb.AddBnActFn.apply(self._bn_meta(bn, relu), a, b, bn.weight, bn.bias, post)
 
     def basic_block(self, blocks, xs):
         ok = torch.is_grad_enabled() and all(
