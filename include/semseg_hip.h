@@ -501,6 +501,29 @@ int ssa_global_avg_pool_fwd(const void* x, int ldx, int B, long HW, int C, void*
 int ssa_global_avg_pool_bwd(const void* dout, int B, long HW, int C, void* dx,
                             void* stream);
 
+/* ------------------------------------------------------- depthwise 3x3 conv ----
+ * nn.Conv2d(C, C, 3, stride, padding = dilation, dilation, groups = C, bias = False), the first half of every
+ * SeparableConv2d of the Xception-71 trunk (network/xception.py:30-32; fixed_padding is symmetric for a 3x3 kernel).
+ * NHWC 16-bit, C % 8 == 0, pixel strides % 8 and >= C, 16-byte aligned operands; w = the parameter's own
+ * [C][1][3][3] fp32 storage.  A bad descriptor returns -1 before the device is touched.                        */
+typedef struct ssa_dwconv_desc {
+  int B, H, W, C, ldx;     /* x [B,H,W,C] */
+  int Ho, Wo, ldy;         /* y [B,Ho,Wo,C], Ho = (H-1)/stride + 1 */
+  int stride, dil;         /* stride 1 with dil >= 1, or stride 2 with dil 1; padding = dil */
+} ssa_dwconv_desc;
+/* y = round16(sum_taps w x).  stats (training; replaces the ssa_bn_stats pass of `self.bn`, xception.py:33,38):
+ * sum y and sum y^2 of the values AS STORED are added into [ssa_bn_stat_replicas()][2][C] fp64 (caller clears).
+ * coef (inference; replaces `self.bn` itself): rows 0 / 1 of the layer's [4][C] table, z = round16(scale * y + shift)
+ * on the rounded y, then the ReLU if relu != 0 -- ssa_bn_apply on the stored y bit for bit.  Both: SSA_EUNSUPPORTED. */
+int ssa_dwconv3x3(const ssa_dwconv_desc* d, const void* x, const float* w, void* y, double* stats,
+                  const float* coef, int relu, void* stream);
+/* Backward of the same conv (cuDNN's backward-data and backward-filter behind the grouped nn.Conv2d) in one pass over
+ * dy and x: dx (nullable) [B,H,W,C] 16-bit, every pixel written; dw (nullable) [C][9] fp32, added to when accumulate
+ * != 0.  ws: ssa_dwconv3x3_bwd_plan's bytes of workspace (the workgroups' fp32 partial sums of dw; needed with dw). */
+int ssa_dwconv3x3_bwd_plan(const ssa_dwconv_desc* d, size_t* ws_bytes);
+int ssa_dwconv3x3_bwd(const ssa_dwconv_desc* d, const void* x, const void* dy, int lddy, const float* w,
+                      void* dx, int lddx, float* dw, int accumulate, void* ws, void* stream);
+
 /* Label-map resize, mask.resize(size, Image.NEAREST) of
  * transforms/joint_transforms.py:193,267,290,319,339,364,466:
  * uint8 [B,Hs,Ws] -> [B,Hd,Wd], dst[y,x] = src[iy_table[y], ix_table[x]].  The

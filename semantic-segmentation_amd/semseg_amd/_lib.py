@@ -73,6 +73,11 @@ class ConvDesc(ctypes.Structure):
         "stride", "pad", "dil", "transposed", "Kpad", "out_f32", "cfg")]
 
 
+class DwConvDesc(ctypes.Structure):
+    """Mirror of ssa_dwconv_desc."""
+    _fields_ = [(n, c_int) for n in ("B", "H", "W", "C", "ldx", "Ho", "Wo", "ldy", "stride", "dil")]
+
+
 class JitterProgram(ctypes.Structure):
     """Mirror of ssa_jitter_program (36 bytes)."""
     _fields_ = [("n_ops", c_int), ("op", c_int * 4), ("factor", c_float * 3), ("hue_byte", c_int)]
@@ -163,6 +168,9 @@ _SIGS = {
     "ssa_bilinear_bwd_y": ([_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P], c_int),
     "ssa_maxpool3x3s2_fwd": ([_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P], c_int),
     "ssa_maxpool3x3s2_bwd": ([_P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P], c_int),
+    "ssa_dwconv3x3": ([POINTER(DwConvDesc), _P, _P, _P, _P, _P, c_int, _P], c_int),
+    "ssa_dwconv3x3_bwd_plan": ([POINTER(DwConvDesc), POINTER(c_size_t)], c_int),
+    "ssa_dwconv3x3_bwd": ([POINTER(DwConvDesc), _P, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P], c_int),
     "ssa_global_avg_pool_fwd": ([_P, c_int, c_int, c_long, c_int, _P, _P], c_int),
     "ssa_global_avg_pool_bwd": ([_P, c_int, c_long, c_int, _P, _P], c_int),
     "ssa_resize_nearest_u8": ([_P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P], c_int),

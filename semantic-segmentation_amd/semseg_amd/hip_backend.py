@@ -29,7 +29,7 @@ import weakref
 
 import torch
 
-from ._lib import lib, check, ConvDesc, PackJob, BnUpdateJob, BnEvalJob, ProfileRec
+from ._lib import lib, check, ConvDesc, DwConvDesc, PackJob, BnUpdateJob, BnEvalJob, ProfileRec
 
 from ._lib import ACT as _ACT_NAME     # storage format of the activations = the library build (SSA_ACT_DTYPE)
 ACT_DTYPE = torch.float16 if _ACT_NAME == "fp16" else torch.bfloat16
@@ -2113,6 +2113,99 @@ class GlobalAvgPoolFn(torch.autograd.Function):
         dx = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dout.device)
         check(lib().ssa_global_avg_pool_bwd(_p(dout), B, H * W, C, _p(dx), _s()), "ssa_global_avg_pool_bwd")
         return dx
+
+
+# --------------------------------------------------------------------------
+# depthwise 3x3 conv (network/xception.py:24-40, the first half of SeparableConv2d)
+# --------------------------------------------------------------------------
+def _dw_operands(x, weight):
+    """(x as dense pixels, ldx, the [C,1,3,3] weight as the kernel reads it: fp32, its own storage when it can be)."""
+    assert x.dim() == 4 and x.dtype == ACT_DTYPE, "depthwise conv takes NHWC %s" % ACT_DTYPE
+    C = x.shape[3]
+    assert tuple(weight.shape) == (C, 1, 3, 3) and C % 8 == 0, (tuple(weight.shape), C)
+    x, ldx = _pixels(x)
+    if x.data_ptr() % 16 or ldx % 8:
+        x, ldx = x.contiguous(), C
+    w = weight.detach()
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    return x, ldx, w
+
+
+def _dw_desc(x, ldx, stride, dil, ldy):
+    B, H, W, C = x.shape
+    return DwConvDesc(B, H, W, C, ldx, (H - 1) // stride + 1, (W - 1) // stride + 1, ldy, stride, dil)
+
+
+def _dwconv_fwd(x, ldx, w, stride, dil, stats=None, coef=None, relu=False):
+    B, H, W, C = x.shape
+    d = _dw_desc(x, ldx, stride, dil, C)
+    y = torch.empty((B, d.Ho, d.Wo, C), dtype=ACT_DTYPE, device=x.device)
+    _note(18.0 * B * d.Ho * d.Wo * C, 2.0 * C * (B * H * W + B * d.Ho * d.Wo))
+    check(lib().ssa_dwconv3x3(ctypes.byref(d), _p(x), _p(w), _p(y), _p(stats), _p(coef), int(bool(relu)), _s()), "ssa_dwconv3x3")
+    return y
+
+
+def dwconv_bn_infer(weight, meta, gamma, beta, x, stride, dil, relu=False):
+    """Inference: depthwise conv with its BatchNorm (evaluation mode) as the epilogue -- ssa_bn_apply on the stored conv
+    output bit for bit, one launch instead of two.  None where the form is not eligible (the caller runs the two)."""
+    if not _FUSE_EVAL_BN or meta.training or not meta.infer or x.dtype != ACT_DTYPE or x.shape[3] % 8:
+        return None
+    g = gamma.detach() if gamma is not None else None
+    b = beta.detach() if beta is not None else None
+    coef = _BN_EVAL.get(meta, g, b, x.shape[3], x.device)
+    if coef is None:
+        return None
+    x, ldx, w = _dw_operands(x, weight)
+    return _dwconv_fwd(x, ldx, w, stride, dil, coef=coef, relu=relu)
+
+
+class DwConv3x3Fn(torch.autograd.Function):
+    """nn.Conv2d(C, C, 3, stride, padding = dil, dil, groups = C, bias = False) on NHWC: x 16-bit, weight [C,1,3,3] fp32.
+    want_stats: the kernel also takes the batch statistics of its stored output and leaves them for the BatchNorm that
+    consumes it (_PENDING_STATS, as the conv epilogues and AddBnActFn do).  Backward: one pass for dx and dW
+    (ssa_dwconv3x3_bwd) on the current stream; a parameter's gradient is added into its gradient-arena slice."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, dil, want_stats):
+        x, ldx, w = _dw_operands(x, weight)
+        C = x.shape[3]
+        stats = _ARENA.take(stat_replicas() * 2 * C, x.device) if want_stats else None
+        y = _dwconv_fwd(x, ldx, w, stride, dil, stats=stats)
+        if stats is not None:
+            _PENDING_STATS[y.data_ptr()] = (stats, stat_replicas())      # picked up (SyncBN: exchanged) by _bn_train_fwd
+        ctx.save_for_backward(x, weight)
+        ctx.meta = (ldx, stride, dil)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        ldx, stride, dil = ctx.meta
+        B, H, W, C = x.shape
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if dy is None or not (need_dx or need_dw):
+            return None, None, None, None, None
+        dyb, lddy = _dz_bf16(dy, C)
+        _, _, w = _dw_operands(x, weight)
+        d = _dw_desc(x, ldx, stride, dil, C)
+        dx = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=x.device) if need_dx else None
+        dw = ws = None
+        param = need_dw and _is_param(weight)
+        if need_dw:
+            dw = _GRADS.slot(weight) if param else torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
+            n = ctypes.c_size_t(0)
+            check(lib().ssa_dwconv3x3_bwd_plan(ctypes.byref(d), ctypes.byref(n)), "ssa_dwconv3x3_bwd_plan")
+            # the workgroups' partial sums: written before they are read, freed with this node (the caching allocator
+            # hands the block to the next layer's; a captured step replays the same addresses)
+            ws = torch.empty((n.value // 4,), dtype=torch.float32, device=x.device)
+        _note(18.0 * B * d.Ho * d.Wo * C * (int(need_dx) + int(need_dw)),
+              2.0 * C * (B * d.Ho * d.Wo + B * H * W * (int(need_dx) + int(need_dw))))
+        check(lib().ssa_dwconv3x3_bwd(ctypes.byref(d), _p(x), _p(dyb), lddy, _p(w), _p(dx), C, _p(dw), int(param), _p(ws),
+                                      _s()), "ssa_dwconv3x3_bwd")
+        if need_dw and not param and dw.dtype != weight.dtype:
+            dw = dw.to(weight.dtype)
+        return dx, (None if param or not need_dw else dw), None, None, None
 
 
 def image_to_nhwc(images, out_hw=None, cpad=16):

@@ -2,7 +2,8 @@
 the `--arch deepv3.DeepV3PlusR50` of BASELINE.json configs[0].  Same factory
 name, call contract and state_dict (363 keys); NHWC bf16 on the HIP kernels.
 `DeepV3PlusW38` / `DeepV3PlusW38I` (network/deepv3.py:108-114): the same head on
-the WiderResNet-38 trunk of scripts/train_cityscapes_deepv3.yml."""
+the WiderResNet-38 trunk of scripts/train_cityscapes_deepv3.yml; `DeepV3PlusX71` (network/deepv3.py:117-118): on the
+Xception-71 trunk (network/xception.py)."""
 import torch
 from torch import nn
 
@@ -103,3 +104,7 @@ def DeepV3PlusW38(num_classes, criterion):
 
 def DeepV3PlusW38I(num_classes, criterion):
     return DeepV3Plus(num_classes, trunk="wrn38", criterion=criterion, init_all=True)
+
+
+def DeepV3PlusX71(num_classes, criterion):
+    return DeepV3Plus(num_classes, trunk="xception71", criterion=criterion)

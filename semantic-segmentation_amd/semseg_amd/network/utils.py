@@ -11,7 +11,8 @@ from ..nn import Conv2d, Norm2d, BNReLU, conv_bn  # noqa: F401  (BNReLU re-expor
 
 def get_trunk(trunk_name, output_stride=8):
     """network/utils.py:102-141 -- the trunks of BASELINE.json's configs: HRNetV2-W48
-    (hot path) and ResNet-50 (DeepLabV3+ plumbing config), and WiderResNet-38 (scripts/train_cityscapes_deepv3.yml)."""
+    (hot path) and ResNet-50 (DeepLabV3+ plumbing config), WiderResNet-38 (scripts/train_cityscapes_deepv3.yml) and
+    Xception-71 (deepv3.DeepV3PlusX71)."""
     assert output_stride == 8, "Only stride8 supported right now"
     if trunk_name == "hrnetv2":
         from . import hrnetv2
@@ -23,7 +24,10 @@ def get_trunk(trunk_name, output_stride=8):
     if trunk_name == "wrn38":
         from .wider_resnet import wrn38
         return wrn38(pretrained=True), 128, 256, 4096
-    raise ValueError("unsupported trunk {} (supported: hrnetv2, resnet-50, wrn38)".format(trunk_name))
+    if trunk_name == "xception71":
+        from .xception import xception71
+        return xception71(output_stride=output_stride, pretrained=True), 64, 128, 2048
+    raise ValueError("unsupported trunk {} (supported: hrnetv2, resnet-50, wrn38, xception71)".format(trunk_name))
 
 
 class AttnHead(nn.Sequential):

@@ -71,6 +71,32 @@ class BackendBase:
         s = self.sum_act([a, b], relu=False)
         return s, self.batch_norm_act(s, bn, None, relu, post)
 
+    def depthwise_conv(self, x, weight, stride, dilation, want_stats=False):
+        """nn.Conv2d(C, C, 3, stride, padding = dilation, dilation, groups = C, bias = False) (network/xception.py:29-37;
+        fixed_padding is symmetric for a 3x3 kernel).  One problem.  Here a composition on the backend's own dense conv,
+        so that every backend applies its own rounding model: the [C,1,3,3] weight scattered onto the diagonal of a
+        dense [C,C,3,3] filter by a differentiable index write (the other products are exact zeros).  The HIP backend
+        runs the depthwise kernels."""
+        assert not _is_list(x), "depthwise_conv takes one problem"
+        C = weight.shape[0]
+        idx = torch.arange(C, device=weight.device)
+        dense = weight.new_zeros((C, C) + tuple(weight.shape[2:])).index_put((idx, idx), weight[:, 0])
+        return self._conv2d(x, dense, None, stride, dilation, dilation)
+
+    def depthwise_conv_bn(self, sep, x):
+        """The first half of a SeparableConv2d (network/xception.py:35-38): depthwise 3x3 -> sep.bn, no ReLU.  One problem."""
+        dw = sep.conv1
+        assert dw.groups == dw.in_channels == dw.out_channels and dw.kernel_size == (3, 3) and dw.bias is None and \
+            dw.padding[0] in (0, dw.dilation[0])
+        y = self.depthwise_conv(x, dw.weight, dw.stride[0], dw.dilation[0], want_stats=sep.bn.training)
+        return self._batch_norm_act(y, sep.bn, None, False, None)
+
+    def separable_conv_bn_act(self, sep, bn, x, residual=None, relu=False):
+        """SeparableConv2d + the BatchNorm behind it (network/xception.py:24-40, 62-64): depthwise 3x3 -> sep.bn ->
+        pointwise 1x1 -> bn (+ residual, ReLU).  One problem."""
+        assert not _is_list(x), "separable_conv_bn_act takes one problem"
+        return self.conv_bn_act(sep.pointwise, bn, self.depthwise_conv_bn(sep, x), residual, relu)
+
     def basic_block(self, blocks, xs):
         """conv3x3-BN-ReLU-conv3x3-BN-(+x)-ReLU (network/hrnetv2.py:37-66, no downsample branch)
         of blocks[i] on xs[i]."""
@@ -151,6 +177,10 @@ class HipBackend(BackendBase):
             flat += [xi, w, b]
         ys = self.hb.ConvGroupFn.apply(spec, *flat)
         return list(ys) if multi else ys[0]
+
+    def _conv2d(self, x, weight, bias, stride, padding, dilation, out_f32=False):
+        """One problem through conv2d: what BackendBase's compositions (depthwise_conv's dense form) call."""
+        return HipBackend.conv2d(self, x, weight, bias, stride, padding, dilation, out_f32)
 
     def _bn_meta(self, bn, relu):
         track = bn.training and bn.track_running_stats and bn.running_mean is not None
@@ -234,6 +264,25 @@ class HipBackend(BackendBase):
             # inference (ssa_sum_act, then the evaluation apply) and forms the fused passes are not built for
             return BackendBase.add_bn_act(self, a, b, bn, relu, post)
         return self.hb.AddBnActFn.apply(self._bn_meta(bn, relu), a, b, bn.weight, bn.bias, post)
+
+    def depthwise_conv(self, x, weight, stride, dilation, want_stats=False):
+        assert not _is_list(x), "depthwise_conv takes one problem"
+        return self.hb.DwConv3x3Fn.apply(x, weight, int(stride), int(dilation), bool(want_stats))
+
+    def depthwise_conv_bn(self, sep, x):
+        """Training: the inner BatchNorm's statistics ride on the depthwise kernel (no ssa_bn_stats pass).  Inference
+        (SSA_FUSE_EVAL_BN): the inner BatchNorm is the depthwise kernel's epilogue.  (The outer BatchNorm of
+        separable_conv_bn_act rides on the pointwise conv either way: conv_bn_act.)"""
+        inner, dw = sep.bn, sep.conv1
+        assert dw.groups == dw.in_channels == dw.out_channels and dw.kernel_size == (3, 3) and dw.bias is None and \
+            dw.padding[0] in (0, dw.dilation[0])
+        if not torch.is_grad_enabled() and not inner.training:
+            y = self.hb.dwconv_bn_infer(dw.weight, self._bn_meta(inner, False), inner.weight, inner.bias, x, dw.stride[0],
+                                        dw.dilation[0])
+            if y is not None:
+                return y
+        y = HipBackend.depthwise_conv(self, x, dw.weight, dw.stride[0], dw.dilation[0], want_stats=inner.training)
+        return HipBackend.batch_norm_act(self, y, inner)
 
     def basic_block(self, blocks, xs):
         ok = torch.is_grad_enabled() and all(

@@ -2,7 +2,8 @@
 """One training step of deepv3.DeepV3PlusW38 (scripts/train_cityscapes_deepv3.yml: 800 x 800 crop, cross entropy, SGD) on
 the device: the reference's loop body through semseg_amd.graph_training (a replayed hipGraph), timed with a host clock
 around a device synchronise.
-    python tools/wrn38_step.py [--crop 800] [--batch 1] [--steps 10] [--warmup 3] [--eager] [--json FILE]
+    python tools/wrn38_step.py [--arch deepv3.DeepV3PlusW38] [--crop 800] [--batch 1] [--steps 10] [--warmup 3] [--eager] [--json FILE]
+(tools/x71_step.py is this tool with --arch deepv3.DeepV3PlusX71 as the default.)
 Storage format = library build: SSA_ACT_DTYPE=bf16 (default) | fp16 (with the dynamic loss scaler of semseg_amd.amp).
 For the per-kernel table run it under the profiler in a run of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/wrn38_step.py --steps 3 --eager"""
@@ -18,8 +19,9 @@ for p in (ROOT, os.path.join(ROOT, "semantic-segmentation_amd")):
 import torch  # noqa: E402
 
 
-def main():
+def main(default_arch="deepv3.DeepV3PlusW38"):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", default=default_arch, help="a factory of semseg_amd.network (get_model)")
     ap.add_argument("--crop", type=int, default=800)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -27,7 +29,7 @@ def main():
     ap.add_argument("--eager", action="store_true", help="eager launches instead of the captured step")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "wrn38_step needs a GPU"
+    assert torch.cuda.is_available(), "the step tools need a GPU"
     import semseg_amd
     import __graft_entry__ as ge
     from semseg_amd import _lib, amp
@@ -35,7 +37,7 @@ def main():
     from semseg_amd.loss.optimizer import FusedSGD
     from semseg_amd.network import get_model
     torch.manual_seed(0)
-    net = get_model("deepv3.DeepV3PlusW38", 19, CrossEntropyLoss2d(ignore_index=255)).cuda().train()
+    net = get_model(a.arch, 19, CrossEntropyLoss2d(ignore_index=255)).cuda().train()
     optim = FusedSGD(net.parameters(), lr=1e-3, momentum=0.9, weight_decay=1e-4)
     net, optim = amp.initialize(net, optim)                 # the loss scaler on the fp16 build, nothing on bf16
     run, opt = (net, optim) if a.eager else semseg_amd.graph_training(net, optim)
@@ -59,7 +61,7 @@ def main():
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
     times.sort()
-    rec = {"arch": "deepv3.DeepV3PlusW38", "crop": a.crop, "batch": a.batch, "dtype": _lib.ACT, "graph": not a.eager,
+    rec = {"arch": a.arch, "crop": a.crop, "batch": a.batch, "dtype": _lib.ACT, "graph": not a.eager,
            "steps": a.steps, "step_ms_median": round(times[len(times) // 2], 3), "step_ms_min": round(times[0], 3),
            "step_ms_max": round(times[-1], 3), "loss": round(float(loss.detach()), 5), "lib_sha": _lib.built_sha(),
            "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
