@@ -763,6 +763,48 @@ int ssa_gblur_crop_flip_normalize(const unsigned char* img_hwc, int H, int W, in
                                   const double* lut256, const float* mean3, const float* std3, void* out_nhwc,
                                   int cpad, void* stream);
 
+/* RandAugment on the device (datasets/randaugment.py: RandAugment 250-263, augment_list 179-201, affine_transform
+ * 16-22, the operations 25-142; datasets/__init__.py:83-87 applies it under --rand_augment N,M to the cropped and
+ * mirrored pair, before ColorJitter): the 14 operations of augment_list, each bit-identical to the Pillow call the
+ * reference makes (csrc/randaugment.hip states the arithmetic).  The op codes are the indices of augment_list.
+ * A program is the drawn chain in application order.  value[k] is the SIGNED value the operation was called with, after
+ * its own sign draw: the shear (ShearX 25-29, ShearY 32-36), the translation in pixels (TranslateX 39-45, TranslateY
+ * 48-54), the angle in degrees (Rotate 71-78), the Solarize threshold (101-104), the Posterize bits 4..8 (107-111), the
+ * blend factor of Color, Brightness, Sharpness (127-142); unused by Identity (175-176), AutoContrast (81-83), Invert
+ * (86-88), Equalize (91-93).  matrix[k] holds, for the five geometric operations, the six coefficients handed to
+ * Image.transform(size, AFFINE, ...), prepared on the host in fp64 (Rotate: Image.rotate's rounded matrix about the
+ * window's centre); a Rotate whose angle is a multiple of 360 degrees is a copy and its matrix is not read.
+ * It is a HOST struct: the entry point reads it and passes each kernel its own small argument block by value. */
+enum { SSA_RANDAUG_IDENTITY = 0, SSA_RANDAUG_SHEARX = 1, SSA_RANDAUG_SHEARY = 2, SSA_RANDAUG_TRANSLATEX = 3,
+       SSA_RANDAUG_TRANSLATEY = 4, SSA_RANDAUG_ROTATE = 5, SSA_RANDAUG_AUTOCONTRAST = 6, SSA_RANDAUG_INVERT = 7,
+       SSA_RANDAUG_EQUALIZE = 8, SSA_RANDAUG_SOLARIZE = 9, SSA_RANDAUG_POSTERIZE = 10, SSA_RANDAUG_COLOR = 11,
+       SSA_RANDAUG_BRIGHTNESS = 12, SSA_RANDAUG_SHARPNESS = 13, SSA_RANDAUG_N_OPS = 14 };
+#define SSA_RANDAUG_MAX_OPS 8
+typedef struct ssa_randaug_program {
+  int n_ops;                              /* 0..SSA_RANDAUG_MAX_OPS */
+  int op[SSA_RANDAUG_MAX_OPS];            /* SSA_RANDAUG_* */
+  double value[SSA_RANDAUG_MAX_OPS];
+  double matrix[SSA_RANDAUG_MAX_OPS][6];
+} ssa_randaug_program;
+
+/* datasets/randaugment.py:256-263 (RandAugment.__call__ with the draws already made) on the window (x0, y0, cw, ch) of
+ * img_hwc (uint8 [H][W][3] on the device) and of lab_hw (uint8 [H][W], or NULL: the image alone), mirrored first under
+ * `flip`: img_out uint8 [ch][cw][3], lab_out uint8 [ch][cw].  Only the geometric operations touch the labels (NEAREST,
+ * fill = ignore_label, the reference's fillmask); the image fill is (0, 0, 0).  img_tmp / lab_tmp: a second buffer of the
+ * output's size, needed when more than one operation rewrites the image / the labels (the launches alternate between the
+ * two; the last one writes the output).  hist: 768 uint32 per AutoContrast / Equalize of the program, ZEROED by the caller
+ * in stream order; the tables of those two are derived from it on the device, so nothing here waits for the device or
+ * reads from it, and the sequence can be captured into a graph.  Launches: one per operation on the image, one per
+ * geometric operation on the labels, one histogram per AutoContrast / Equalize, and one crop / flip copy when no
+ * operation rewrites the image or the labels.  Returns -1 before touching the device on a null image or output, an empty
+ * or outside window, an op code outside 0..13, more than SSA_RANDAUG_MAX_OPS operations, Posterize bits outside 4..8, a
+ * value or coefficient that is not finite, a missing buffer; -2 for a nearest-neighbour warp of a window larger than 8192
+ * in either direction (Pillow's 16.16 sums leave its 32-bit integers there).  The outputs must not overlap the inputs. */
+int ssa_randaug_u8(const unsigned char* img_hwc, const unsigned char* lab_hw, int H, int W, int x0, int y0, int cw,
+                   int ch, int flip, const ssa_randaug_program* program, int ignore_label, unsigned int* hist,
+                   unsigned char* img_out, unsigned char* img_tmp, unsigned char* lab_out, unsigned char* lab_tmp,
+                   void* stream);
+
 /* Evaluation tail on the device (utils/trnval_utils.py:173-196 + utils/misc.py:50-67
  * fast_hist): pred[p] = first argmax_c logits[p,c] (uint8, optional) and
  * hist[gt*C + pred] += 1 for 0 <= gt < C (int64 [C*C], ACCUMULATED: clear it once per

@@ -88,6 +88,11 @@ class GblurTaps(ctypes.Structure):
     _fields_ = [("radius", c_int), ("w", c_double * 6)]
 
 
+class RandaugProgram(ctypes.Structure):
+    """Mirror of ssa_randaug_program (488 bytes)."""
+    _fields_ = [("n_ops", c_int), ("op", c_int * 8), ("value", c_double * 8), ("matrix", (c_double * 6) * 8)]
+
+
 _P = c_void_p
 _SIGS = {
     "ssa_version": ([], c_int),
@@ -218,6 +223,8 @@ _SIGS = {
                       _P, _P, _P], c_int),
     "ssa_gblur_crop_flip_normalize": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(JitterProgram), _P,
                                        POINTER(GblurTaps), _P, _P, _P, _P, c_int, _P], c_int),
+    "ssa_randaug_u8": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(RandaugProgram), c_int, _P, _P, _P,
+                        _P, _P, _P], c_int),
     "ssa_confusion_matrix": ([_P, c_int, _P, c_long, c_int, _P, _P, _P], c_int),
     "ssa_eval_tail": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P,
                        _P, _P], c_int),

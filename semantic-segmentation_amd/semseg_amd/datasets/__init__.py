@@ -6,3 +6,4 @@ from .transforms import nearest_index_table, resize_labels_nearest   # noqa: F40
 from .transforms import (ColorJitter, JitterParams, adjust_brightness, adjust_contrast, adjust_hue,   # noqa: F401
                          adjust_saturation, color_jitter, crop_flip_normalize)
 from .transforms import BlurParams, RandomGaussianBlur, gaussian_blur, gaussian_taps   # noqa: F401
+from .transforms import AugmentParams, RandAugment, rand_augment   # noqa: F401

@@ -62,7 +62,7 @@ def resize_labels_nearest(mask, size):
 MEAN_STD = ([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])      # config.py:96-97 (cfg.DATASET.MEAN / STD)
 
 
-def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitter=None, blur=None):
+def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitter=None, blur=None, augment=None):
     """img_u8: uint8 CUDA [H,W,3] (RGB, as np.array(PIL image)); labels_u8: uint8 CUDA [H,W] or None;
     window = (x0, y0, w, h) as PIL's crop box origin + size; flip: mirror the cropped pair.
     jitter: None, or the JitterParams of ColorJitter.get_params -- the image-only augmentation the reference runs
@@ -71,16 +71,24 @@ def crop_flip_normalize(img_u8, labels_u8, window, flip, mean_std=MEAN_STD, jitt
     blur: None, or the BlurParams of RandomGaussianBlur.get_params -- the reference's --gblur step, which follows the
     jitter (datasets/__init__.py:102): the window goes through ssa_gblur_crop_flip_normalize instead, which runs the
     jitter program (if any; ssa_jitter_luma_sum first) on the pixels it stages, blurs and normalises in one launch.
+    augment: None, or the AugmentParams of RandAugment.get_params -- the reference's --rand_augment step, a JOINT
+    transform that runs on the cropped, mirrored pair before the jitter (datasets/__init__.py:83-87): the chain goes
+    through ssa_randaug_u8 first, and the jitter (its luma sum taken over the augmented window), the blur, the normalise
+    and the label conversion then read what it wrote.  With None nothing changes.
     Returns (image [1,h,w,16] bf16 NHWC -- hand it to the network's trunk --, labels [1,h,w] int64)."""
     from .._lib import lib, check
     assert img_u8.dtype == torch.uint8 and img_u8.is_cuda and img_u8.dim() == 3 and img_u8.shape[2] == 3
     H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
     x0, y0, cw, ch = (int(v) for v in window)
+    if labels_u8 is not None:
+        assert labels_u8.dtype == torch.uint8 and labels_u8.is_cuda and tuple(labels_u8.shape) == (H, W)
+    if augment is not None:       # the pair the later steps read is the augmented window: whole, not mirrored again
+        img_u8, labels_u8 = rand_augment(img_u8, labels_u8, augment, (x0, y0, cw, ch), flip)
+        H, W, x0, y0, flip = ch, cw, 0, 0, False
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     out = _image_half(img_u8, (x0, y0, cw, ch), flip, jitter, blur, True, mean_std)
     gts = None
     if labels_u8 is not None:
-        assert labels_u8.dtype == torch.uint8 and labels_u8.is_cuda and tuple(labels_u8.shape) == (H, W)
         labels_u8 = labels_u8.contiguous()
         gts = torch.empty((1, ch, cw), dtype=torch.int64, device=img_u8.device)
         check(lib().ssa_label_u8_crop_flip(ctypes.c_void_p(labels_u8.data_ptr()), H, W, x0, y0, cw, ch,
@@ -403,6 +411,169 @@ class RandomGaussianBlur:
 
     def __call__(self, img_u8):
         return gaussian_blur(img_u8, self.get_params())
+
+
+# ---------------------------------------------------------------------------------------------
+# RandAugment on the device (datasets/randaugment.py; datasets/__init__.py:83-87 inserts RandAugment(N, M) under
+# --rand_augment N,M after RandomSizeAndCrop and RandomHorizontallyFlip): a JOINT transform of the cropped, mirrored
+# (image, labels) pair -- N operations drawn from the 14 of augment_list, each bit-identical to the Pillow call the
+# reference makes (csrc/randaugment.hip).  The draws stay on the host and consume Python's `random` as the reference
+# does; what travels to the kernels is the drawn program.
+# ---------------------------------------------------------------------------------------------
+RANDAUG_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "AutoContrast", "Invert",
+               "Equalize", "Solarize", "Posterize", "Color", "Brightness", "Sharpness")   # index = SSA_RANDAUG_*
+# augment_list's (minval, maxval), datasets/randaugment.py:179-201
+RANDAUG_RANGES = ((0., 1.0), (0., 0.3), (0., 0.3), (0., 0.33), (0., 0.33), (0, 30), (0, 1), (0, 1), (0, 1), (0, 110),
+                  (4, 8), (0.1, 1.9), (0.1, 1.9), (0.1, 1.9))
+RANDAUG_GEOMETRIC = RANDAUG_OPS[1:6]              # the operations that draw a sign and move the labels
+RANDAUG_MAX_OPS = 8                               # SSA_RANDAUG_MAX_OPS
+
+
+def rotate_matrix(angle, w, h):
+    """The six coefficients Image.rotate(angle) hands to Image.transform for a w x h image (no centre, no translation,
+    no expansion; angle % 360 != 0): the rounded rotation about (w / 2, h / 2), operation by operation as Pillow's
+    Python code derives it."""
+    import math
+    angle = -math.radians(angle % 360.0)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0,
+         round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    cx, cy = w / 2.0, h / 2.0
+    x, y = -cx, -cy
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+class AugmentParams:
+    """One drawn RandAugment chain: `ops` = [(name of RANDAUG_OPS, signed value)] in application order -- the shear, the
+    translation in PIXELS, the angle in degrees, the Solarize threshold, the Posterize bits (int), the blend factor; unused
+    where the operation has no magnitude -- and `size` = (w, h) of the image the operations see."""
+    __slots__ = ("ops", "size")
+
+    def __init__(self, ops, size):
+        self.ops = [(str(op), int(v) if op == "Posterize" else float(v)) for op, v in ops]
+        self.size = (int(size[0]), int(size[1]))
+        if any(op not in RANDAUG_OPS for op, _ in self.ops):
+            raise ValueError("AugmentParams: operations must be names of %s, not %r" % (RANDAUG_OPS, self.ops))
+        if len(self.ops) > RANDAUG_MAX_OPS:
+            raise ValueError("AugmentParams: at most %d operations, not %d" % (RANDAUG_MAX_OPS, len(self.ops)))
+        if any(op == "Posterize" and not 4 <= v <= 8 for op, v in self.ops):
+            raise ValueError("AugmentParams: Posterize keeps 4..8 bits")
+        if self.size[0] <= 0 or self.size[1] <= 0:
+            raise ValueError("AugmentParams: size must be positive, not %r" % (self.size,))
+
+    def __repr__(self):
+        return "AugmentParams(%r, size=%r)" % (self.ops, self.size)
+
+    def histograms(self):
+        """How many operations of the chain need a histogram of the image."""
+        return sum(op in ("AutoContrast", "Equalize") for op, _ in self.ops)
+
+    def matrix(self, k):
+        """The affine coefficients of the k-th operation (zeros where it is not geometric or is a copy)."""
+        op, v = self.ops[k]
+        w, h = self.size
+        if op == "ShearX":
+            return [1.0, v, 0.0, 0.0, 1.0, 0.0]
+        if op == "ShearY":
+            return [1.0, 0.0, 0.0, v, 1.0, 0.0]
+        if op == "TranslateX":
+            return [1.0, 0.0, v, 0.0, 1.0, 0.0]
+        if op == "TranslateY":
+            return [1.0, 0.0, 0.0, 0.0, 1.0, v]
+        if op == "Rotate" and v % 360.0 != 0:
+            return rotate_matrix(v, w, h)
+        return [0.0] * 6
+
+    def program(self):
+        """-> the ssa_randaug_program the entry point takes."""
+        from .._lib import RandaugProgram
+        pg = RandaugProgram()
+        pg.n_ops = len(self.ops)
+        for k, (op, v) in enumerate(self.ops):
+            pg.op[k] = RANDAUG_OPS.index(op)
+            pg.value[k] = float(v)
+            for j, c in enumerate(self.matrix(k)):
+                pg.matrix[k][j] = float(c)
+        return pg
+
+
+def rand_augment(img_u8, labels_u8, params, window=None, flip=False, ignore_label=255):
+    """img_u8: uint8 CUDA [H,W,3]; labels_u8: uint8 CUDA [H,W] or None; params: AugmentParams drawn for the window's size;
+    window = (x0, y0, w, h) or None for the whole image; flip: mirror the pair first.  -> (uint8 [h,w,3], uint8 [h,w] or
+    None) = the drawn chain applied to the cropped, mirrored pair as the reference's RandAugment.__call__ applies it.
+    Only the five geometric operations touch the labels; ignore_label is the reference's fillmask
+    (cfg.DATASET.IGNORE_LABEL), the image fill is (0, 0, 0).  One call of ssa_randaug_u8: the histograms and tables of
+    AutoContrast / Equalize stay on the device, nothing here waits for it."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    if not isinstance(params, AugmentParams):
+        raise TypeError("augment parameters must be an AugmentParams (RandAugment.get_params), not %r" % type(params))
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        raise ValueError("the image must be uint8 [H, W, 3]")
+    img_u8 = img_u8.contiguous()
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    x0, y0, cw, ch = (0, 0, W, H) if window is None else (int(v) for v in window)
+    if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= W and y0 + ch <= H):
+        raise ValueError("window %r is empty or not inside the %d x %d image" % ((x0, y0, cw, ch), W, H))
+    if params.size != (cw, ch):
+        raise ValueError("the parameters were drawn for a %d x %d image, the window is %d x %d" % (params.size + (cw, ch)))
+    if labels_u8 is not None:
+        if labels_u8.dtype != torch.uint8 or tuple(labels_u8.shape) != (H, W):
+            raise ValueError("the labels must be uint8 [H, W] of the image's size")
+        labels_u8 = labels_u8.contiguous()
+    dev = img_u8.device
+    out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=dev)
+    tmp = torch.empty_like(out)
+    lab_out = lab_tmp = None
+    if labels_u8 is not None:
+        lab_out = torch.empty((ch, cw), dtype=torch.uint8, device=dev)
+        lab_tmp = torch.empty_like(lab_out)
+    nh = params.histograms()
+    hist = torch.zeros((nh * 768,), dtype=torch.int32, device=dev) if nh else None    # cleared in stream order
+    pg = params.program()
+    check(lib().ssa_randaug_u8(hb._p(img_u8), hb._p(labels_u8), H, W, x0, y0, cw, ch, int(bool(flip)), ctypes.byref(pg),
+                               int(ignore_label), hb._p(hist), hb._p(out), hb._p(tmp), hb._p(lab_out), hb._p(lab_tmp),
+                               hb._s()), "ssa_randaug_u8")
+    return out, lab_out
+
+
+class RandAugment:
+    """datasets/randaugment.py:250-263 for uint8 CUDA buffers: the same constructor, the same draws from Python's
+    `random` in the same order, the drawn chain applied on the device."""
+
+    def __init__(self, n, m):
+        self.n = n
+        self.m = m      # [0, 30]
+
+    def get_params(self, size):
+        """size = (w, h) of the image the operations will see.  random.choices of n entries of augment_list, then, walking
+        them in order, one random.random() for each of ShearX, ShearY, TranslateX, TranslateY, Rotate (the value is
+        negated when the draw is > 0.5); the others draw nothing -> AugmentParams.  The generator is left in the state the
+        reference's RandAugment(n, m)(img, mask) leaves it in.  m outside [0, 30] fails the reference's asserts."""
+        if not 0 <= self.m <= 30:
+            raise ValueError("RandAugment: the magnitude m must be in [0, 30], not %r" % (self.m,))
+        w, h = int(size[0]), int(size[1])
+        chosen = random.choices(range(len(RANDAUG_OPS)), k=self.n)
+        ops = []
+        for i in chosen:
+            op, (minval, maxval) = RANDAUG_OPS[i], RANDAUG_RANGES[i]
+            val = (float(self.m) / 30) * float(maxval - minval) + minval
+            if op in RANDAUG_GEOMETRIC:
+                if random.random() > 0.5:
+                    val = -val
+                if op == "TranslateX":
+                    val = val * w
+                elif op == "TranslateY":
+                    val = val * h
+            elif op == "Posterize":
+                val = int(val)
+            ops.append((op, val))
+        return AugmentParams(ops, (w, h))
+
+    def __call__(self, img_u8, labels_u8):
+        return rand_augment(img_u8, labels_u8, self.get_params((int(img_u8.shape[1]), int(img_u8.shape[0]))))
 
 
 class DevicePrefetcher:
