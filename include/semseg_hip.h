@@ -665,6 +665,47 @@ int ssa_rmi_bwd_logits_bce(const float* logits, int ld, const int64_t* labels, i
                            const float* bce_grad, double bce_coef, const double* bce_acc, double bce_denom_add,
                            float* dlogits, void* stream);
 
+/* Label relaxation (--jointwtborder): ImgWtLossSoftNLL, loss/utils.py:150-231, on the target of
+ * RelaxedBoundaryLossToTensor, transforms/transforms.py:74-123 (K16).  The [C+1,H,W] multi-hot target never exists
+ * on the training path: a pixel's class SET is two 64-bit words, sets[p][2], bit c = class c, bit C = the ignore
+ * channel (1 <= C <= 127, otherwise SSA_EUNSUPPORTED).  stats is int64 [B][C+2] per image: the number of set entries
+ * of each of the C+1 channels (what calculate_weights sums, loss/utils.py:165-177), then the number of pixels whose
+ * set holds no real class (`ignore_mask`, loss/utils.py:212).  Integer sums: exact, whatever the order.
+ *
+ * ssa_relax_mask_labels: transforms/transforms.py:90-117.  labels [B][H][W], int64 or (label_u8) uint8; a label equal
+ * to ignore_index or outside [0, C) is class C (the rule of ssa_rmi_pool); the set of a pixel is the union of the
+ * labels of its (2*border+1)^2 window, positions outside the image counting as C (`shift(..., cval=num_classes)`);
+ * border 0, 1 or 2 (cfg.BORDER_WINDOW), otherwise SSA_EUNSUPPORTED.  strict_lo/strict_hi: cfg.STRICTBORDERCLASS as a
+ * bit set (0, 0 = None): a pixel whose own label is in it keeps the one-hot of that label (transforms.py:95-99,114).
+ * Clears stats itself, by a small launch in front of the kernel.                                                    */
+int ssa_relax_mask_labels(const void* labels, int label_u8, int B, int H, int W, int C, int ignore_index, int border,
+                          unsigned long long strict_lo, unsigned long long strict_hi, unsigned long long* sets,
+                          int64_t* stats, void* stream);
+/* The same from the reference's own target, uint8 [B][C+1][H][W], non-zero = set (loss/utils.py:207-213).         */
+int ssa_relax_mask_multihot(const unsigned char* multihot, int B, int H, int W, int C, unsigned long long* sets,
+                            int64_t* stats, void* stream);
+/* sets -> uint8 [B][C+1][H][W] of 0 / 1: what RelaxedBoundaryLossToTensor.__call__ returns (transforms.py:117-123). */
+int ssa_relax_multihot(const unsigned long long* sets, int B, int H, int W, int C, unsigned char* out, void* stream);
+/* calculate_weights, loss/utils.py:165-177, and `torch.Tensor(class_weights)` of :227: w[B][C] fp32 =
+ * (float)((hist != 0) * upper_bound * (1 - hist) + 1) with hist = count / total in fp64, total over all C+1 channels;
+ * batch_weights (cfg.BATCH_WEIGHTING, :218-219): the counts summed over the batch first, every row the same.
+ * Also zeroes acc[B], the accumulators of ssa_relax_nll_fwd.                                                       */
+int ssa_relax_weights(const int64_t* stats, int B, int C, double upper_bound, int batch_weights, float* w,
+                      double* acc, void* stream);
+/* custom_nll, loss/utils.py:179-205, per image i over its H*W pixels: acc[i] += -q[p] * (sum_{c in set} w[i][c]) *
+ * log(sum_{c in set} softmax(x)[c]), 0 where the set holds no real class;  q[p] = sum_b 1 / max(1, |set_b[p]|) over
+ * ALL images of the batch (`border_weights` is passed whole at :228 and broadcasts at :196).  logits fp32 NHWC
+ * [B*H*W][C] with leading dimension ld >= C.  acc must be zero (ssa_relax_weights).                               */
+int ssa_relax_nll_fwd(const float* logits, int ld, const unsigned long long* sets, const float* w, int B, int H, int W,
+                      int C, double* acc, void* stream);
+/* loss = sum_i acc[i] / (H*W - stats[i][C+1] + 1)  (loss/utils.py:203-204,229) -> fp32 scalar                     */
+int ssa_relax_nll_finalize(const double* acc, const int64_t* stats, int B, int H, int W, int C, float* loss,
+                           void* stream);
+/* Backward of the two above, recomputed from the logits (as ssa_bce_bwd): dlogits dense [B*H*W][C] =
+ * upstream[0] / (H*W - stats[i][C+1] + 1) * q * (sum_{c in set} w[i][c]) * (softmax[k] - [k in set] softmax[k] / S). */
+int ssa_relax_nll_bwd(const float* logits, int ld, const unsigned long long* sets, const float* w, const int64_t* stats,
+                      int B, int H, int W, int C, const float* upstream, float* dlogits, void* stream);
+
 /* Tail of the input pipeline on the device: joint crop window + optional
  * horizontal flip of the cropped pair (transforms/joint_transforms.py:276-281
  * RandomHorizontallyFlip after the crop transforms), then for the image ToTensor + Normalize

@@ -7,7 +7,7 @@ exceptions, e.g. network/ocrnet.py:105).
 """
 import ctypes
 import os
-from ctypes import c_int, c_long, c_float, c_double, c_void_p, c_size_t, POINTER
+from ctypes import c_int, c_long, c_float, c_double, c_void_p, c_size_t, c_uint64, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # Storage format of the 16-bit activations = which build of the library the process runs on (csrc/common.h):
@@ -210,6 +210,13 @@ _SIGS = {
                             c_double, _P, c_int, _P], c_int),
     "ssa_rmi_bwd_logits_bce": ([_P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_double, _P, c_double, _P,
                                 c_double, _P, _P], c_int),
+    "ssa_relax_mask_labels": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_uint64, c_uint64, _P, _P, _P], c_int),
+    "ssa_relax_mask_multihot": ([_P, c_int, c_int, c_int, c_int, _P, _P, _P], c_int),
+    "ssa_relax_multihot": ([_P, c_int, c_int, c_int, c_int, _P, _P], c_int),
+    "ssa_relax_weights": ([_P, c_int, c_int, c_double, c_int, _P, _P, _P], c_int),
+    "ssa_relax_nll_fwd": ([_P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
+    "ssa_relax_nll_finalize": ([_P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
+    "ssa_relax_nll_bwd": ([_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P], c_int),
     "ssa_image_u8_crop_flip_normalize": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P],
                                          c_int),
     "ssa_resample_u8": ([_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P], c_int),

@@ -44,7 +44,11 @@ def _defaults():
     c.LOSS = AttrDict(OCR_ALPHA=0.4, OCR_AUX_RMI=False, SUPERVISED_MSCALE_WT=0)   # config.py:150-155
     c.DATASET = AttrDict(NUM_CLASSES=19, IGNORE_LABEL=255)
     c.OPTIONS = AttrDict(INIT_DECODER=False)
+    c.EPOCH = 0                      # config.py:50 (train.py sets it every epoch)
+    c.BATCH_WEIGHTING = False        # config.py:55 (class weights over the batch instead of per image)
+    c.BORDER_WINDOW = 1              # config.py:58 (half width of the label relaxation window)
     c.REDUCE_BORDER_EPOCH = -1       # config.py:60 (the 'scl-poly' LR schedule switches there)
+    c.STRICTBORDERCLASS = None       # config.py:62 (classes whose pixels are never relaxed)
     return c
 
 
@@ -66,6 +70,10 @@ def sync_from_reference(ref_cfg):
     cfg.DATASET.IGNORE_LABEL = ref_cfg.DATASET.IGNORE_LABEL
     cfg.OPTIONS.INIT_DECODER = ref_cfg.OPTIONS.INIT_DECODER
     cfg.REDUCE_BORDER_EPOCH = getattr(ref_cfg, "REDUCE_BORDER_EPOCH", -1)
+    cfg.EPOCH = getattr(ref_cfg, "EPOCH", 0)
+    cfg.BATCH_WEIGHTING = getattr(ref_cfg, "BATCH_WEIGHTING", False)
+    cfg.BORDER_WINDOW = getattr(ref_cfg, "BORDER_WINDOW", 1)
+    cfg.STRICTBORDERCLASS = getattr(ref_cfg, "STRICTBORDERCLASS", None)
     assert not cfg.MODEL.ALIGN_CORNERS, "only align_corners=False is implemented"
     for k in ("MSCALE_OLDARCH", "MSCALE_DROPOUT", "MSCALE_CAT_SCALE_FLT"):      # config.py:132-135
         assert not getattr(m, k, False), "cfg.MODEL.%s is not on the accelerated path" % k

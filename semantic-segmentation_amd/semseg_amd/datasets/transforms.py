@@ -616,3 +616,31 @@ class DevicePrefetcher:
                     if torch.is_tensor(t):
                         t.record_stream(torch.cuda.current_stream(self.device))
             yield cur
+
+
+# ---------------------------------------------------------------------------------------------
+# Boundary label relaxation (transforms/transforms.py:74-123): the [C+1,H,W] multi-hot target of
+# --jointwtborder from a label map that is already on the device.  The training path does not go
+# through here -- ImgWtLossSoftNLL relaxes the int64 labels of crop_flip_normalize itself and never
+# materialises this tensor; the class is for users who want the tensor.
+class RelaxedBoundaryLossToTensor(object):
+    """Device label map, uint8 or int64, [H,W] or [B,H,W] -> uint8 [C+1,H,W] or [B,C+1,H,W]: channel c of a pixel is 1
+    iff a pixel of its (2*cfg.BORDER_WINDOW+1)^2 window has label c; `ignore_id`, labels outside [0, C) and positions
+    outside the image are the extra channel C; pixels whose own label is in cfg.STRICTBORDERCLASS keep its one-hot."""
+
+    def __init__(self, ignore_id, num_classes):
+        self.ignore_id = ignore_id
+        self.num_classes = num_classes
+
+    def __call__(self, img):
+        from .. import hip_backend as hb
+        from ..config import cfg
+        if cfg.REDUCE_BORDER_EPOCH != -1 and cfg.EPOCH > cfg.REDUCE_BORDER_EPOCH:
+            raise NotImplementedError("the reduced-border mode (--rlx_off_epoch, cfg.EPOCH > cfg.REDUCE_BORDER_EPOCH) "
+                                      "is not on the accelerated path")
+        assert torch.is_tensor(img) and img.dim() in (2, 3), "a label map [H,W] or [B,H,W] on the device"
+        squeeze = img.dim() == 2
+        sets, _ = hb.relax_class_sets(img.unsqueeze(0) if squeeze else img, self.num_classes, self.ignore_id,
+                                      cfg.BORDER_WINDOW, cfg.STRICTBORDERCLASS)
+        out = hb.relax_multihot(sets, self.num_classes)
+        return out[0] if squeeze else out

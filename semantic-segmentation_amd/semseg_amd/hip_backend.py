@@ -2497,6 +2497,90 @@ class CrossEntropyFn(torch.autograd.Function):
         return g, None, None
 
 
+def strict_bits(strict, classes):
+    """cfg.STRICTBORDERCLASS (None or a list of class ids) as the two 64-bit words of the C ABI."""
+    bits = 0
+    for c in (strict or ()):
+        c = int(c)
+        if 0 <= c < classes:
+            bits |= 1 << c
+    return bits & ((1 << 64) - 1), bits >> 64
+
+
+def relax_class_sets(target, classes, ignore_index=255, border=1, strict=None):
+    """The per-pixel class sets of the label relaxation and their counts: `target` is a label map [B,H,W] (int64 or
+    uint8; transforms/transforms.py:90-117 is applied to it) or the reference's own multi-hot target uint8
+    [B,C+1,H,W].  Returns (sets int64 [B,H,W,2]: bit c = class c, bit C = the ignore channel; stats int64 [B,C+2]: set
+    entries per channel, then the pixels without a real class).  Two launches: the counters' clearing and the kernel."""
+    L = lib()
+    C = int(classes)
+    target = target.contiguous()
+    if target.dim() == 4:
+        assert target.dtype == torch.uint8 and target.shape[1] == C + 1, "a multi-hot target is uint8 [B, C+1, H, W]"
+        B, _, H, W = target.shape
+    else:
+        assert target.dim() == 3 and target.dtype in (torch.int64, torch.uint8), "label maps are int64 or uint8 [B, H, W]"
+        B, H, W = target.shape
+    sets = torch.empty((B, H, W, 2), dtype=torch.int64, device=target.device)
+    stats = torch.empty((B, C + 2), dtype=torch.int64, device=target.device)
+    if target.dim() == 4:
+        check(L.ssa_relax_mask_multihot(_p(target), B, H, W, C, _p(sets), _p(stats), _s()), "ssa_relax_mask_multihot")
+    else:
+        lo, hi = strict_bits(strict, C)
+        check(L.ssa_relax_mask_labels(_p(target), 1 if target.dtype == torch.uint8 else 0, B, H, W, C, int(ignore_index),
+                                      int(border), lo, hi, _p(sets), _p(stats), _s()), "ssa_relax_mask_labels")
+    return sets, stats
+
+
+def relax_multihot(sets, classes):
+    """uint8 [B,C+1,H,W] of 0 / 1 from the class sets: RelaxedBoundaryLossToTensor's tensor (transforms.py:117-123)."""
+    B, H, W, _ = sets.shape
+    out = torch.empty((B, int(classes) + 1, H, W), dtype=torch.uint8, device=sets.device)
+    check(lib().ssa_relax_multihot(_p(sets), B, H, W, int(classes), _p(out), _s()), "ssa_relax_multihot")
+    return out
+
+
+class RelaxNllFn(torch.autograd.Function):
+    """ImgWtLossSoftNLL (loss/utils.py:150-231) on label maps or on the reference's multi-hot target.  Forward:
+    five launches (the counters' clearing, class sets + counts, class weights, loss, finalize); nothing of the [C+1,H,W] target
+    exists and nothing comes back to the host.  The forward saves no gradient: the backward recomputes it from the
+    logits, already scaled, in one launch (as BceRmiFn does)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, classes, ignore_index, border, strict, upper_bound, batch_weights):
+        L = lib()
+        logits, ld = _pixels(logits.float())
+        B, H, W, C = logits.shape
+        assert C == int(classes), "logits have %d channels, the criterion %d classes" % (C, int(classes))
+        assert target.shape[0] == B and tuple(target.shape[-2:]) == (H, W), "target and logits differ in shape"
+        dev = logits.device
+        sets, stats = relax_class_sets(target, C, ignore_index, border, strict)
+        w = torch.empty((B, C), dtype=torch.float32, device=dev)
+        acc = torch.empty((B,), dtype=torch.float64, device=dev)
+        check(L.ssa_relax_weights(_p(stats), B, C, float(upper_bound), 1 if batch_weights else 0, _p(w), _p(acc), _s()),
+              "ssa_relax_weights")
+        check(L.ssa_relax_nll_fwd(_p(logits), ld, _p(sets), _p(w), B, H, W, C, _p(acc), _s()), "ssa_relax_nll_fwd")
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        check(L.ssa_relax_nll_finalize(_p(acc), _p(stats), B, H, W, C, _p(loss), _s()), "ssa_relax_nll_finalize")
+        ctx.ld = ld
+        ctx.save_for_backward(logits, sets, w, stats)
+        ctx.mark_non_differentiable(sets, stats, w)
+        ctx.set_materialize_grads(False)        # (no zero tensors for the three integer-side outputs in backward)
+        return loss, sets, stats, w
+
+    @staticmethod
+    def backward(ctx, up, *_):
+        if up is None:
+            return (None,) * 8
+        logits, sets, w, stats = ctx.saved_tensors
+        B, H, W, C = logits.shape
+        up = up.float().contiguous()
+        g = torch.empty((B, H, W, C), dtype=torch.float32, device=logits.device)
+        check(lib().ssa_relax_nll_bwd(_p(logits), ctx.ld, _p(sets), _p(w), _p(stats), B, H, W, C, _p(up), _p(g), _s()),
+              "ssa_relax_nll_bwd")
+        return g, None, None, None, None, None, None, None
+
+
 class BceRmiFn(torch.autograd.Function):
     """RMILoss.forward_sigmoid: masked BCE, optionally 0.5*bce + 0.5*rmi.  On dense logits the forward saves NO
     gradient: the backward recomputes (sigmoid - onehot) from the logits, already scaled (ssa_bce_bwd, or inside the RMI

@@ -49,12 +49,42 @@ class RMILoss(nn.Module):
         return ops.backend().bce_rmi(x, labels_4D, bool(do_rmi), self.weight_lambda)
 
 
+def _reduced_border():
+    """loss/utils.py:183-184, transforms/transforms.py:103: the reduced-border mode of --rlx_off_epoch"""
+    return cfg.REDUCE_BORDER_EPOCH != -1 and cfg.EPOCH > cfg.REDUCE_BORDER_EPOCH
+
+
+class ImgWtLossSoftNLL(nn.Module):
+    """loss/utils.py:150-231, the label relaxation loss of --jointwtborder.  `target` is the label map [B,H,W] (int64
+    or uint8) -- the relaxation of transforms/transforms.py:74-123 then happens on the device, inside the criterion
+    -- or the reference's own multi-hot target, uint8 [B,C+1,H,W].  cfg.BORDER_WINDOW, cfg.STRICTBORDERCLASS and
+    cfg.BATCH_WEIGHTING are read at call time."""
+
+    def __init__(self, classes, ignore_index=255, weights=None, upper_bound=1.0, norm=False):
+        super().__init__()
+        assert weights is None and not norm
+        self.num_classes = classes
+        self.ignore_index = ignore_index
+        self.upper_bound = upper_bound
+
+    def forward(self, inputs, target, do_rmi=None):
+        if _reduced_border():
+            raise NotImplementedError("the reduced-border mode (--rlx_off_epoch, cfg.EPOCH > cfg.REDUCE_BORDER_EPOCH) "
+                                      "is not on the accelerated path")
+        return ops.backend().relax_nll(_nhwc_f32(inputs), target, self.num_classes, self.ignore_index,
+                                       border=cfg.BORDER_WINDOW, strict=cfg.STRICTBORDERCLASS,
+                                       upper_bound=self.upper_bound, batch_weights=bool(cfg.BATCH_WEIGHTING))
+
+
 def get_loss(args):
-    """loss/utils.py:40-67 (the two criteria the hot-path recipes use)."""
+    """loss/utils.py:40-67 (the criteria the hot-path recipes use)."""
     if getattr(args, "rmi_loss", False):
         criterion = RMILoss(num_classes=cfg.DATASET.NUM_CLASSES, ignore_index=cfg.DATASET.IGNORE_LABEL).cuda()
-    elif getattr(args, "img_wt_loss", False) or getattr(args, "jointwtborder", False):
-        raise NotImplementedError("only --rmi_loss and plain cross entropy are on the accelerated path")
+    elif getattr(args, "img_wt_loss", False):
+        raise NotImplementedError("--img_wt_loss is not on the accelerated path")
+    elif getattr(args, "jointwtborder", False):
+        criterion = ImgWtLossSoftNLL(classes=cfg.DATASET.NUM_CLASSES, ignore_index=cfg.DATASET.IGNORE_LABEL,
+                                     upper_bound=getattr(args, "wt_bound", 1.0)).cuda()
     else:
         criterion = CrossEntropyLoss2d(ignore_index=cfg.DATASET.IGNORE_LABEL).cuda()
     criterion_val = CrossEntropyLoss2d(weight=None, ignore_index=cfg.DATASET.IGNORE_LABEL).cuda()

@@ -390,6 +390,13 @@ class HipBackend(BackendBase):
             self.hb._no_fp16_training()
         return self.hb.CrossEntropyFn.apply(logits, labels, ignore_index)
 
+    def relax_nll(self, logits, target, classes, ignore_index, border=1, strict=None, upper_bound=1.0,
+                  batch_weights=False):
+        if logits.requires_grad and torch.is_grad_enabled():
+            self.hb._no_fp16_training()
+        return self.hb.RelaxNllFn.apply(logits, target, classes, ignore_index, border, strict, upper_bound,
+                                        batch_weights)[0]
+
     def bce_rmi(self, logits, labels, do_rmi, weight_lambda=0.5):
         if logits.requires_grad and torch.is_grad_enabled():
             self.hb._no_fp16_training()
