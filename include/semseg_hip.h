@@ -186,6 +186,19 @@ int ssa_conv2d_halo_reg_supported(const ssa_conv_desc* d);
 int ssa_conv2d_halo_reg(const ssa_conv_desc* d, const void* x, const void* w_frag, const float* bias,
                         void* y, double* stats, void* stream);
 
+/* 5x5 stride-1 pad-2 convs of the Deeper (Panoptic-DeepLab style) decoders and their data gradients (conv_up2 320->256
+ * at stride 4, conv_up3 288->256 at stride 2: cuDNN behind ConvBnRelu(.., kernel_size=5, padding=2) at
+ * network/deeper.py:53-54 and network/mscale.py:382-383).  The kernel of ssa_conv2d_halo_reg with 25 taps: 128 pixels x
+ * 256 channels per 4-wave workgroup, filter fragments from global memory straight into the MFMA registers, the 8 x 36
+ * pixel halo tile of each 48 / 64-channel chunk by LDS DMA, double buffered: one workgroup barrier per chunk
+ * (csrc/conv_halo5.hip).  Same operands as ssa_conv2d_halo_reg (w_frag: ssa_pack_filter mode 2 / 3, k = (kh, kw, ci),
+ * Kpad = 25 * Cin); Cin % 48 == 0 or % 64 == 0; 16-bit output only; stats as for ssa_conv2d_tile.
+ * ssa_conv2d_halo5_supported() adds the size policy (W >= 32 and >= 16384 pixels: smaller problems stay on
+ * ssa_conv2d_igemm); the entry point itself takes any size.                                                         */
+int ssa_conv2d_halo5_supported(const ssa_conv_desc* d);
+int ssa_conv2d_halo5(const ssa_conv_desc* d, const void* x, const void* w_frag, const float* bias,
+                     void* y, double* stats, void* stream);
+
 /* Tile configuration ssa_conv2d_igemm would use for this problem
  * (0: 128x128, 1: 256x64, 2: 128x96, 3: 256x32, 4: 64x64, 5: 128x64 tiles). */
 int ssa_conv2d_igemm_tile(const ssa_conv_desc* d);

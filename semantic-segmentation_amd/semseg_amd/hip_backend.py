@@ -604,6 +604,12 @@ def halo_supported(d):
     return bool(lib().ssa_conv2d_halo_supported(ctypes.byref(d)))
 
 
+def halo5_supported(d):
+    """The 5x5 stride-1 pad-2 kernel (csrc/conv_halo5.hip) takes this problem and the library's size policy keeps it
+    there (the Deeper decoders' conv_up2 / conv_up3 and their data gradients)."""
+    return bool(lib().ssa_conv2d_halo5_supported(ctypes.byref(d)))
+
+
 def wide_supported(d):
     """The 256 x 256 GEMM (csrc/conv_gemm_wide.hip) takes this 1x1 problem and is the better choice for it."""
     return bool(lib().ssa_conv2d_gemm_wide_supported(ctypes.byref(d)))
@@ -646,16 +652,18 @@ def _igemm(x, ldx, geom_in, wp, Kpad, bias, geom_out, Cout, k, stride, pad, dil,
     return y
 
 
-def _tile_conv(d, x, wfrag, bias, stats, halo=False, aux=None, ldaux=0, coef=None, mode=0, wide=False):
+def _tile_conv(d, x, wfrag, bias, stats, halo=False, aux=None, ldaux=0, coef=None, mode=0, wide=False, halo5=False):
     """Halo-staged conv launch: conv_tile.hip (small-channel 3x3 convs; aux = fused epilogue tile of
-    the data gradient, see ssa_conv2d_tile_aux) or conv_halo_gemm.hip (large-channel 3x3 / 1x1)."""
+    the data gradient, see ssa_conv2d_tile_aux), conv_halo_gemm.hip (large-channel 3x3 / 1x1) or conv_halo5.hip (5x5)."""
     y = torch.empty((d.B, d.Ho, d.Wo, d.Cout), dtype=torch.float32 if d.out_f32 else ACT_DTYPE,
                     device=x.device)
     P = d.B * d.Ho * d.Wo
     _note(2.0 * P * d.Cout * d.Cin * d.KH * d.KW,
           _conv_bytes(P, d.Cin, P, d.Cout, (d.KH, d.KW), 4 if d.out_f32 else 2) + (2.0 * P * d.Cout if mode else 0.0))
     L = lib()
-    if wide:
+    if halo5:
+        check(L.ssa_conv2d_halo5(ctypes.byref(d), _p(x), _p(wfrag), _p(bias), _p(y), _p(stats), _s()), "ssa_conv2d_halo5")
+    elif wide:
         check(L.ssa_conv2d_gemm_wide(ctypes.byref(d), _p(x), _p(wfrag), _p(bias), _p(y), _p(stats), _s()), "ssa_conv2d_gemm_wide")
     elif not halo and bias is None and tile_p_supported(d):
         check(L.ssa_conv2d_tile_p(ctypes.byref(d), _p(x), _p(wfrag), None, _p(y), _p(stats),
@@ -738,12 +746,13 @@ def _conv_fwd(x, ldx, weight, b, stride, pad, dil, out_f32, want_stats):
     use_tile = al and tile_supported(td)
     use_wide = (not use_tile) and al and wide_supported(td)          # (the library's policy: csrc/conv_gemm_wide.hip)
     use_halo = (not use_tile) and (not use_wide) and al and halo_supported(td)
+    use_halo5 = (KH, KW) == (5, 5) and al and halo5_supported(td)     # (no other kernel above takes a 5x5 filter)
     stats = None
-    if want_stats and not out_f32 and not (_NO_IGEMM_STATS and not (use_tile or use_halo or use_wide)):
+    if want_stats and not out_f32 and not (_NO_IGEMM_STATS and not (use_tile or use_halo or use_wide or use_halo5)):
         stats = _ARENA.take(stat_replicas() * 2 * Cout, x.device)
-    if use_tile or use_halo or use_wide:
+    if use_tile or use_halo or use_wide or use_halo5:
         wp, _ = _packed_filter(weight, 2, Cin, 0)
-        y = _tile_conv(td, x, wp, b, stats, halo=use_halo, wide=use_wide)
+        y = _tile_conv(td, x, wp, b, stats, halo=use_halo, wide=use_wide, halo5=use_halo5)
     else:
         wp, Kpad = _packed_filter(weight, 0, Cin, 0)
         y = _igemm(x, ldx, (B, H, W, Cin), wp, Kpad, b, (Ho, Wo), Cout, (KH, KW), stride, pad, dil, False,
@@ -773,11 +782,13 @@ def _conv_dgrad(x_shape, weight, dyb, lddy, cout_pad, stride, pad, dil, out_hw, 
     use_tile = al and tile_supported(td)
     use_wide = (not use_tile) and al and not mode and wide_supported(td)
     use_halo = (not use_tile) and (not use_wide) and al and halo_supported(td)
+    use_halo5 = (KH, KW) == (5, 5) and al and not mode and halo5_supported(td)
     if mode:
         assert use_tile
-    if use_tile or use_halo or use_wide:
+    if use_tile or use_halo or use_wide or use_halo5:
         wpt, _ = _packed_filter(weight, 3, 0, cout_pad)
-        return _tile_conv(td, dyb, wpt, None, stats, halo=use_halo, aux=aux, ldaux=ldaux, coef=coef, mode=mode, wide=use_wide)
+        return _tile_conv(td, dyb, wpt, None, stats, halo=use_halo, aux=aux, ldaux=ldaux, coef=coef, mode=mode, wide=use_wide,
+                          halo5=use_halo5)
     if _DGRAD_S2 and stride == 2 and (KH, KW) == (3, 3) and pad == 1 and dil == 1 and Cin % 8 == 0 and al and \
             lddy % 8 == 0 and (Ho, Wo) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1):
         return _dgrad_s2(x_shape, weight, dyb, lddy, cout_pad, out_hw)
@@ -1492,7 +1503,7 @@ def conv_bn_infer_group(convs, metas, gammas, betas, xs, ress, relus):
         Wo = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
         td = _tile_desc(B, H, W, Cin, ldx, Cout, (KH, KW), stride, pad, dil, Ho, Wo, False)
         on_tile_p = conv.bias is None and tile_p_supported(td)
-        if not on_tile_p and (tile_supported(td) or wide_supported(td) or halo_supported(td)):
+        if not on_tile_p and (tile_supported(td) or wide_supported(td) or halo_supported(td) or halo5_supported(td)):
             continue                                    # conv_tile.hip / the head kernels: no such epilogue (yet)
         res, ldr = (None, 0)
         if ress[i] is not None:

@@ -1,19 +1,22 @@
 """Multi-scale-attention models without the OCR head (network/mscale.py of the
-reference): `mscale.HRNet` (MscaleBasic), `mscale.HRNet_ASP` (ASPP) and
-`mscale.DeepV3R50` (MscaleV3Plus) -- the sibling `--arch` names of SURVEY.md 8f
+reference): `mscale.HRNet` (MscaleBasic), `mscale.HRNet_ASP` (ASPP),
+`mscale.DeepV3R50` / `DeepV3W38` / `DeepV3W38Fuse` / `DeepV3W38Fuse2` / `DeepV3X71` (MscaleV3Plus) and
+`mscale.DeeperW38` / `DeeperX71` (MscaleDeeper: the Panoptic-DeepLab style decoder of network/deeper.py plus a
+scale-attention head) -- the sibling `--arch` names of SURVEY.md 8f
 rank 4 -- on the same HIP operator surface as ocrnet.MscaleOCR.  Same factories,
 call contract and state_dict keys; NHWC bf16 inside.
 
 Not carried over: `nscale_fused_forward` (mscale.py:95-122) -- the reference's
 `recurse_fuse_fwd` passes `attn_lo=` to `_fwd` (mscale.py:77), which none of its
-models accepts, so that entry point raises TypeError there too; MscaleDeeper and
-the wrn38 / xception71 / efficientnet factories need trunks outside
-BASELINE.json's configs (get_trunk lists the supported ones)."""
+models accepts, so that entry point raises TypeError there too; `DeeperEffB4`, `DeepV3EffB4` and `DeepV3EffB4Fuse`
+(mscale.py:349-356, 445-447) -- the reference ships no EfficientNet trunk file and its own get_trunk raises for
+'efficientnet_b4' (get_trunk here lists the supported trunks)."""
 from .. import ops
 from ..config import cfg
 from ..nn import Conv2d, initialize_weights
+from .deeper import DeeperDecoder
 from .deepv3 import get_aspp
-from .mynn import Upsample
+from .mynn import Upsample, Upsample2
 from .ocrnet import _Base, _nchw, fmt_scale
 from .utils import get_trunk, make_attn_head, make_seg_head
 
@@ -144,6 +147,79 @@ class MscaleV3Plus(MscaleBase):
 
 def DeepV3R50(num_classes, criterion):
     return MscaleV3Plus(num_classes, trunk="resnet-50", criterion=criterion)
+
+
+def DeepV3W38(num_classes, criterion):
+    return MscaleV3Plus(num_classes, trunk="wrn38", criterion=criterion)
+
+
+def DeepV3W38Fuse(num_classes, criterion):
+    return MscaleV3Plus(num_classes, trunk="wrn38", criterion=criterion, fuse_aspp=True)
+
+
+def DeepV3W38Fuse2(num_classes, criterion):
+    return MscaleV3Plus(num_classes, trunk="wrn38", criterion=criterion, fuse_aspp=True, attn_2b=True)
+
+
+def DeepV3X71(num_classes, criterion):
+    return MscaleV3Plus(num_classes, trunk="xception71", criterion=criterion)
+
+
+def _no_effnet(name):
+    raise ValueError("mscale.{}: no EfficientNet trunk (the reference's get_trunk raises for it as well)".format(name))
+
+
+def DeepV3EffB4(num_classes, criterion):
+    _no_effnet("DeepV3EffB4")
+
+
+def DeepV3EffB4Fuse(num_classes, criterion):
+    _no_effnet("DeepV3EffB4Fuse")
+
+
+class MscaleDeeper(MscaleBase, DeeperDecoder):
+    """Panoptic-DeepLab style decoder with a scale-attention head on its 256-channel stride-2 features
+    (mscale.py:363-432)."""
+
+    def __init__(self, num_classes, trunk="wrn38", criterion=None, fuse_aspp=False, attn_2b=False):
+        super().__init__()
+        self.criterion = criterion
+        self.fuse_aspp = fuse_aspp
+        self.attn_2b = attn_2b
+        self.backbone, s2_ch, s4_ch, high_level_ch = get_trunk(trunk_name=trunk, output_stride=8)
+        self.aspp, aspp_out_ch = get_aspp(high_level_ch, bottleneck_ch=256, output_stride=8)
+        self._make_decoder(s2_ch, s4_ch, aspp_out_ch, num_classes)
+        self.scale_attn = make_attn_head(in_ch=256, out_ch=2 if attn_2b else 1)
+        if cfg.OPTIONS.INIT_DECODER:
+            initialize_weights(self.convs2, self.convs4, self.conv_up1, self.conv_up2, self.conv_up3, self.conv_up5,
+                               self.scale_attn)
+
+    def _fwd(self, x, size, aspp_lo=None, aspp_attn=None):
+        B = ops.backend()
+        s2_features, s4_features, final_features = self.backbone(x)
+        aspp = self.aspp(final_features)
+        if self.fuse_aspp and aspp_lo is not None and aspp_attn is not None:
+            tgt = aspp.shape[1:3]
+            a = B.bilinear(aspp_attn, tgt)
+            aspp = B.to_act(B.attn_blend(B.bcast_mul(a, B.bilinear(aspp_lo, tgt)), a, aspp))
+        up3 = self._decode(aspp, s2_features, s4_features)
+        out = Upsample2(self.conv_up5(up3, out_f32=True), out_f32=True)
+        scale_attn = Upsample2(self.scale_attn(up3), out_f32=True)
+        if self.attn_2b:
+            return out, scale_attn[..., 0:1], scale_attn[..., 1:], aspp
+        return out, scale_attn, scale_attn, aspp
+
+
+def DeeperW38(num_classes, criterion, s2s4=True):
+    return MscaleDeeper(num_classes=num_classes, criterion=criterion, trunk="wrn38")
+
+
+def DeeperX71(num_classes, criterion, s2s4=True):
+    return MscaleDeeper(num_classes=num_classes, criterion=criterion, trunk="xception71")
+
+
+def DeeperEffB4(num_classes, criterion, s2s4=True):
+    _no_effnet("DeeperEffB4")
 
 
 class MscaleBasic(MscaleBase):

@@ -30,6 +30,20 @@ def get_trunk(trunk_name, output_stride=8):
     raise ValueError("unsupported trunk {} (supported: hrnetv2, resnet-50, wrn38, xception71)".format(trunk_name))
 
 
+class ConvBnRelu(nn.Module):
+    """conv -> BatchNorm (eps 1e-5) -> ReLU with children conv / bn / relu (network/utils.py:144-159); one
+    conv_bn call, so the batch statistics come out of the conv's epilogue."""
+
+    def __init__(self, in_planes, out_planes, kernel_size, stride=1, padding=0, norm_layer=Norm2d):
+        super().__init__()
+        self.conv = Conv2d(in_planes, out_planes, kernel_size=kernel_size, stride=stride, padding=padding, bias=False)
+        self.bn = norm_layer(out_planes, eps=1e-5)
+        self.relu = nn.ReLU(inplace=True)
+
+    def forward(self, x):
+        return conv_bn(self.conv, self.bn, x, relu=True)
+
+
 class AttnHead(nn.Sequential):
     """3x3 -> BN -> ReLU -> 3x3 -> BN -> ReLU -> 1x1 -> sigmoid; children are
     named conv0/bn0/re0/conv1/bn1/re1/conv2/sig as in network/utils.py:348-363."""
