@@ -859,6 +859,28 @@ int ssa_randaug_u8(const unsigned char* img_hwc, const unsigned char* lab_hw, in
                    unsigned char* img_out, unsigned char* img_tmp, unsigned char* lab_out, unsigned char* lab_tmp,
                    void* stream);
 
+/* Class-uniform sampling (--class_uniform_pct, train.py:78, config.py:102): the centroid pass of
+ * class_centroids_image, datasets/uniform.py:84-135, over N label maps of one size (csrc/centroids.hip).
+ * labels: uint8 [N][H][ld] on the device, ld >= W.  Tiles are those of calc_tile_locations (uniform.py:67-81):
+ * H / tile rows by W / tile columns of full tiles, y-major; pixels of the remainder count nowhere; an image smaller
+ * than a tile has no tiles (nothing is launched, SSA_OK).  lut: NULL, or 256 bytes on the device applied to every
+ * label as it is read -- the id2trainid step, uniform.py:112-121, which compares against the untouched copy of the
+ * mask and is therefore a plain table.  1 <= C <= 256; a mapped label >= C (255 = ignore) counts nowhere.
+ * sums: uint64 [N][tiles][C][3] = (pixels of the class in the tile, sum of their tile-local x, of their tile-local
+ * y); cleared by a launch in front.  centroids: int32 [N][tiles][C][2] = (sum_x / n + x_offs, sum_y / n + y_offs)
+ * by integer floor division -- what `int(center_of_mass(...))` gives, uniform.py:127-131 --, (-1, -1) where n == 0;
+ * written by a finalize launch of the same call.  Integer sums: exact, whatever the order.  No host
+ * synchronisation, no allocation; capturable.                                                                      */
+int ssa_class_centroids_u8(const unsigned char* labels, int N, int H, int W, int ld, int tile, int C,
+                           const unsigned char* lut, unsigned long long* sums, int* centroids, void* stream);
+
+/* Constant padding of an image or a label map (csrc/pad_u8.hip): `ImageOps.expand(img, border, fill)` of
+ * RandomCrop.__call__, transforms/joint_transforms.py:163-178, and add_margin, joint_transforms.py:48-60 (called at
+ * 126-141), for RGB and L images.  src: uint8 [H][W][channels] on the device, channels 1 or 3; dst:
+ * [H+top+bottom][W+left+right][channels]; fill: 3 HOST bytes (a label map takes the first).                       */
+int ssa_pad_u8(const unsigned char* src, int H, int W, int channels, int left, int top, int right, int bottom,
+               const unsigned char* fill, unsigned char* dst, void* stream);
+
 /* Evaluation tail on the device (utils/trnval_utils.py:173-196 + utils/misc.py:50-67
  * fast_hist): pred[p] = first argmax_c logits[p,c] (uint8, optional) and
  * hist[gt*C + pred] += 1 for 0 <= gt < C (int64 [C*C], ACCUMULATED: clear it once per

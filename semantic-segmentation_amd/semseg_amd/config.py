@@ -42,13 +42,22 @@ def _defaults():
         ),
     )
     c.LOSS = AttrDict(OCR_ALPHA=0.4, OCR_AUX_RMI=False, SUPERVISED_MSCALE_WT=0)   # config.py:150-155
-    c.DATASET = AttrDict(NUM_CLASSES=19, IGNORE_LABEL=255)
+    c.DATASET = AttrDict(
+        NUM_CLASSES=19, IGNORE_LABEL=255,
+        NAME="",                     # config.py:98 (assert_and_infer_cfg: args.dataset, config.py:244)
+        CLASS_UNIFORM_PCT=0.5,       # config.py:102 (--class_uniform_pct, train.py:78): share of class-uniform items per epoch
+        CLASS_UNIFORM_TILE=1024,     # config.py:103 (--class_uniform_tile): names the centroid cache (datasets/uniform.py)
+        CLASS_UNIFORM_BIAS=None,     # config.py:253: per-class multipliers of the per-class item count, or None
+        CENTROID_ROOT="/home/dcg-adlr-atao-data.cosmos277/assets/uniform_centroids",   # config.py:52, 82-83
+        TRANSLATE_AUG_FIX=False,     # config.py:112 (--translate_aug_fix, config.py:266-267)
+    )
     c.OPTIONS = AttrDict(INIT_DECODER=False)
     c.EPOCH = 0                      # config.py:50 (train.py sets it every epoch)
     c.BATCH_WEIGHTING = False        # config.py:55 (class weights over the batch instead of per image)
     c.BORDER_WINDOW = 1              # config.py:58 (half width of the label relaxation window)
     c.REDUCE_BORDER_EPOCH = -1       # config.py:60 (the 'scl-poly' LR schedule switches there)
     c.STRICTBORDERCLASS = None       # config.py:62 (classes whose pixels are never relaxed)
+    c.DROPOUT_COARSE_BOOST_CLASSES = None   # config.py:350-353 (the auto-labelled branch of the centroid pass: not built)
     return c
 
 
@@ -68,6 +77,10 @@ def sync_from_reference(ref_cfg):
         cfg.LOSS[k] = getattr(ref_cfg.LOSS, k)
     cfg.DATASET.NUM_CLASSES = ref_cfg.DATASET.NUM_CLASSES
     cfg.DATASET.IGNORE_LABEL = ref_cfg.DATASET.IGNORE_LABEL
+    for k in ("NAME", "CLASS_UNIFORM_PCT", "CLASS_UNIFORM_TILE", "CLASS_UNIFORM_BIAS", "CENTROID_ROOT", "TRANSLATE_AUG_FIX"):
+        if hasattr(ref_cfg.DATASET, k):         # (CLASS_UNIFORM_BIAS exists only after assert_and_infer_cfg)
+            cfg.DATASET[k] = getattr(ref_cfg.DATASET, k)
+    cfg.DROPOUT_COARSE_BOOST_CLASSES = getattr(ref_cfg, "DROPOUT_COARSE_BOOST_CLASSES", None)
     cfg.OPTIONS.INIT_DECODER = ref_cfg.OPTIONS.INIT_DECODER
     cfg.REDUCE_BORDER_EPOCH = getattr(ref_cfg, "REDUCE_BORDER_EPOCH", -1)
     cfg.EPOCH = getattr(ref_cfg, "EPOCH", 0)

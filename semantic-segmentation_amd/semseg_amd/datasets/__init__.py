@@ -7,3 +7,6 @@ from .transforms import (ColorJitter, JitterParams, adjust_brightness, adjust_co
                          adjust_saturation, color_jitter, crop_flip_normalize)
 from .transforms import BlurParams, RandomGaussianBlur, gaussian_blur, gaussian_taps   # noqa: F401
 from .transforms import AugmentParams, RandAugment, rand_augment   # noqa: F401
+from .transforms import CropPlan, RandomSizeAndCrop, pad_u8, resize_image_bicubic   # noqa: F401
+from .uniform import (build_centroids, build_epoch, calc_tile_locations, class_centroids, class_centroids_all,   # noqa: F401
+                      class_centroids_image, pooled_class_centroids_all, random_sampling)

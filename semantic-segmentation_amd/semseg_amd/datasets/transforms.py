@@ -644,3 +644,141 @@ class RelaxedBoundaryLossToTensor(object):
                                       cfg.BORDER_WINDOW, cfg.STRICTBORDERCLASS)
         out = hb.relax_multihot(sets, self.num_classes)
         return out[0] if squeeze else out
+
+
+# ---------------------------------------------------------------------------------------------
+# RandomSizeAndCrop (transforms/joint_transforms.py:433-471 over RandomCrop, joint_transforms.py:73-181): the first joint
+# transform of every training recipe, and the one that places the crop over the centroid of a class-uniform item
+# (datasets/base_loader.py:129-132).  The draws stay on the host and consume Python's `random` exactly as the
+# reference does; what they decide travels as a CropPlan, and the device resizes, pads (only where the plan says so:
+# ssa_pad_u8) and hands crop_flip_normalize its window.
+# ---------------------------------------------------------------------------------------------
+class CropPlan:
+    """What one call of the reference's RandomSizeAndCrop decided.
+    scale_amt: the drawn scale (times the pre_size scale), what the reference appends to its result;
+    size = (w, h) of the resized pair; border = (pad_w, pad_h) of ImageOps.expand, each on both sides (joint_transforms.py:
+    165-177); margins = (left, top, right, bottom) of add_margin (TRANSLATE_AUG_FIX, joint_transforms.py:126-141);
+    window = (x0, y0, w, h) of the crop inside the resized and padded pair; centroid: the scaled centroid or None."""
+
+    def __init__(self, scale_amt, size, border, margins, window, centroid):
+        self.scale_amt, self.size, self.border, self.margins = scale_amt, tuple(size), tuple(border), tuple(margins)
+        self.window, self.centroid = tuple(window), None if centroid is None else tuple(centroid)
+
+    @property
+    def pad(self):
+        """(left, top, right, bottom) the device adds around the resized pair."""
+        (bw, bh), (l, t, r, b) = self.border, self.margins
+        return (bw + l, bh + t, bw + r, bh + b)
+
+    def __repr__(self):
+        return "CropPlan(scale_amt=%r, size=%r, border=%r, margins=%r, window=%r, centroid=%r)" % (
+            self.scale_amt, self.size, self.border, self.margins, self.window, self.centroid)
+
+
+def pad_u8(src_u8, pad, fill):
+    """src_u8: uint8 device tensor [H,W] or [H,W,3]; pad = (left, top, right, bottom); fill: an int or three ->
+    the padded copy, what ImageOps.expand / add_margin give for L and RGB images."""
+    from .. import hip_backend as hb
+    from .._lib import lib, check
+    if src_u8.dtype != torch.uint8 or not (src_u8.dim() == 2 or (src_u8.dim() == 3 and src_u8.shape[2] == 3)):
+        raise ValueError("uint8 [H,W] or [H,W,3]")
+    src_u8 = src_u8.contiguous()
+    H, W = int(src_u8.shape[0]), int(src_u8.shape[1])
+    ch = 1 if src_u8.dim() == 2 else 3
+    left, top, right, bottom = (int(v) for v in pad)
+    fill3 = bytes([int(fill)] * 3 if isinstance(fill, int) else [int(v) for v in fill])
+    out = torch.empty((H + top + bottom, W + left + right) + tuple(src_u8.shape[2:]), dtype=torch.uint8,
+                      device=src_u8.device)
+    check(lib().ssa_pad_u8(hb._p(src_u8), H, W, ch, left, top, right, bottom, fill3, hb._p(out), hb._s()), "ssa_pad_u8")
+    return out
+
+
+class RandomSizeAndCrop(object):
+    """transforms/joint_transforms.py:433-471 for uint8 device buffers: the same constructor, the same draws from Python's
+    `random` in the same order.  get_params draws; apply runs the plan on the device."""
+
+    def __init__(self, crop_size, crop_nopad, scale_min=0.5, scale_max=2.0, full_size=False, pre_size=None):
+        from ..config import cfg
+        if isinstance(crop_size, (list, tuple)):
+            self.size = tuple(crop_size)                # (h, w)
+        else:
+            self.size = (int(crop_size), int(crop_size))
+        self.nopad = crop_nopad
+        self.ignore_index = cfg.DATASET.IGNORE_LABEL    # read at construction, as RandomCrop does
+        self.pad_color = (0, 0, 0)
+        self.scale_min, self.scale_max = scale_min, scale_max
+        self.full_size, self.pre_size = full_size, pre_size
+
+    @staticmethod
+    def _crop_in_image(centroid, target_w, target_h, w, h):
+        """joint_transforms.py:101-121 -> (x1, y1)."""
+        if centroid is not None:                        # the crop covers the centroid and stays inside the image
+            c_x, c_y = centroid
+            x1 = min(w - target_w, max(0, random.randint(c_x - target_w, c_x)))
+            y1 = min(h - target_h, max(0, random.randint(c_y - target_h, c_y)))
+        else:                                           # an axis that fits exactly draws nothing
+            x1 = 0 if w == target_w else random.randint(0, w - target_w)
+            y1 = 0 if h == target_h else random.randint(0, h - target_h)
+        return x1, y1
+
+    def get_params(self, size, centroid=None):
+        """size = (w, h) of the pair, centroid = (x, y) of a class-uniform item or None -> CropPlan.  Python's `random`
+        is left in the state RandomSizeAndCrop.__call__ leaves it in: one uniform() for the scale, then RandomCrop's
+        draws -- none when the resized pair already has the crop's size.  As in the reference, the centroid is scaled
+        but NOT moved by a border the crop adds.  A plan whose window does not lie inside the padded pair (the reference
+        reaches one under TRANSLATE_AUG_FIX when only one side is shorter than the crop, and lets Pillow fill the rest
+        with zeros) raises ValueError after the draws."""
+        from ..config import cfg
+        in_w, in_h = int(size[0]), int(size[1])
+        scale_amt = random.uniform(self.scale_min, self.scale_max)
+        if self.pre_size is not None:
+            scale_amt *= self.pre_size / (in_w if in_w > in_h else in_h)
+        if self.full_size:
+            self.size = (in_h, in_w)
+        w, h = int(in_w * scale_amt), int(in_h * scale_amt)
+        if centroid is not None:
+            centroid = [int(c * scale_amt) for c in centroid]
+        resized = (w, h)
+        target_h, target_w = self.size
+        border, margins = (0, 0), (0, 0, 0, 0)
+        if w == target_w and h == target_h:
+            x1, y1 = 0, 0
+        elif cfg.DATASET.TRANSLATE_AUG_FIX and w < target_w and h < target_h:
+            left = random.randint(0, target_w - w)      # the image slides inside the crop
+            top = random.randint(0, target_h - h)
+            margins = (left, top, target_w - w - left, target_h - h - top)
+            x1, y1 = 0, 0
+        else:
+            if cfg.DATASET.TRANSLATE_AUG_FIX:
+                pass
+            elif self.nopad:
+                if target_h > h or target_w > w:
+                    target_h = target_w = min(w, h)
+            else:
+                pad_h = (target_h - h) // 2 + 1 if target_h > h else 0
+                pad_w = (target_w - w) // 2 + 1 if target_w > w else 0
+                border = (pad_w, pad_h)
+                w, h = w + 2 * pad_w, h + 2 * pad_h
+            x1, y1 = self._crop_in_image(centroid, target_w, target_h, w, h)
+        plan = CropPlan(scale_amt, resized, border, margins, (x1, y1, target_w, target_h), centroid)
+        l, t, r, b = plan.pad
+        if not (x1 >= 0 and y1 >= 0 and x1 + target_w <= resized[0] + l + r and y1 + target_h <= resized[1] + t + b):
+            raise ValueError("%r: the crop window is not inside the %d x %d pair" % (plan, resized[0] + l + r,
+                                                                                     resized[1] + t + b))
+        return plan
+
+    def apply(self, plan, img_u8_cuda, labels_u8_cuda):
+        """The plan on the device: bicubic / nearest resize of the pair to plan.size, then -- only where the plan has a
+        border or margins -- the constant padding (image (0, 0, 0), labels the ignore label).  -> (img, labels, window):
+        what crop_flip_normalize(img, labels, window, flip, ...) takes."""
+        w, h = plan.size
+        img = resize_image_bicubic(img_u8_cuda, (h, w))
+        labels = resize_labels_nearest(labels_u8_cuda, (h, w))
+        if any(plan.pad):
+            img = pad_u8(img, plan.pad, self.pad_color)
+            labels = pad_u8(labels, plan.pad, self.ignore_index)
+        return img, labels, plan.window
+
+    def __call__(self, img_u8_cuda, labels_u8_cuda, centroid=None):
+        plan = self.get_params((int(img_u8_cuda.shape[1]), int(img_u8_cuda.shape[0])), centroid)
+        return self.apply(plan, img_u8_cuda, labels_u8_cuda) + (plan.scale_amt,)
