@@ -14,9 +14,11 @@ namespace {
 constexpr int NT = 256;
 
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-  // monotone int mapping trick
-  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
+  // monotone int mapping trick.  The branch goes by the sign BIT: -0.0 (0x80000000 = INT_MIN as an int, never above the
+  // initial -FLT_MAX) belongs to the unsigned-min side, where it orders above every negative value and below +0.0
+  const int b = __float_as_int(v);
+  if (b >= 0) atomicMax(reinterpret_cast<int*>(addr), b);
+  else atomicMin(reinterpret_cast<unsigned int*>(addr), static_cast<unsigned int>(b));
 }
 
 __global__ void hw_init_kernel(float* __restrict__ rowstat, int K) {

@@ -44,6 +44,13 @@ _EXACT_RESAMPLE_F16 = ("exact_bilinear_fwd and (v8-4x-ld or px-c19-4x-in16 or el
                        "or exact_bilinear_autograd and (v8-slices or px16-tile16) or exact_bilinear_upsample_cat "
                        "or exact_bilinear_bounded and c48-16-up or exact_image_resize or exact_pool")
 
+# the exact OCR head tests (csrc/ocr_attn.hip, csrc/ocr.hip through the C ABI and through OcrAttnFn / OcrGatherFn): every
+# case but the two large ones (131,205 pixels of attention, the re-balanced HW softmax over 16,515 pixels x 256 classes),
+# which skip here.  The fp16-storage build runs a tie case per region-block count and two gather cases.
+_EXACT_OCR = "exact_ocr"
+_EXACT_OCR_F16 = ("exact_ocr_attn_tie and (k19-p300 or k65-p300 or k96-p300) or exact_ocr_hw_softmax[k19-13x21 "
+                  "or exact_ocr_gather_autograd[k65")
+
 # (file, -k expression): each entry a few seconds under emulation
 SELECTION = [
     ("tests/test_kernels_gpu.py", "bce_rmi or scale_fusion or cross_entropy or sigmoid or softmax"),
@@ -58,15 +65,18 @@ SELECTION = [
     ("tests/test_kernels_gpu.py", _EXACT),
     ("tests/test_kernels_gpu.py", _EXACT_BN),
     ("tests/test_kernels_gpu.py", _EXACT_RESAMPLE),
+    ("tests/test_exact_ocr_gpu.py", _EXACT_OCR),
 ]
 # how many tests an expression must run: a renamed case id would otherwise silently select fewer
-MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10, _EXACT_BN: 27, _EXACT_BN_F16: 8, _EXACT_RESAMPLE: 115, _EXACT_RESAMPLE_F16: 28}
+MIN_PASSED = {_EXACT: 47, _EXACT_F16: 10, _EXACT_BN: 27, _EXACT_BN_F16: 8, _EXACT_RESAMPLE: 115, _EXACT_RESAMPLE_F16: 28,
+              _EXACT_OCR: 44, _EXACT_OCR_F16: 5}
 
 
 # (file, -k expression, extra environment): the fp16-storage build of the same kernels (its own rounding helpers)
 SELECTION_ENV = [("tests/test_kernels_gpu.py", _EXACT_F16, {"SSA_ACT_DTYPE": "fp16"}),
                  ("tests/test_kernels_gpu.py", _EXACT_BN_F16, {"SSA_ACT_DTYPE": "fp16"}),
-                 ("tests/test_kernels_gpu.py", _EXACT_RESAMPLE_F16, {"SSA_ACT_DTYPE": "fp16"})]
+                 ("tests/test_kernels_gpu.py", _EXACT_RESAMPLE_F16, {"SSA_ACT_DTYPE": "fp16"}),
+                 ("tests/test_exact_ocr_gpu.py", _EXACT_OCR_F16, {"SSA_ACT_DTYPE": "fp16"})]
 
 
 def _passed_enough(expr, tail):
