@@ -911,6 +911,42 @@ int ssa_eval_tail(const float* const* srcs, const int* flips, int n_src, int ld,
                   unsigned char* pred, float* prob, unsigned char* err, int64_t* hist, double* loss_acc,
                   float* avg, void* stream);
 
+/* ImageDumper.dump on the device (utils/misc.py:279-386, driven from train.py:552-597; csrc/dump_tail.hip): one streaming
+ * launch over the H x W pixels p of ONE image.  With u8(v) = v truncated toward zero to a byte,
+ *     input_rgb[p][c] = u8(((image[c*plane_stride + p] - inv_mean3[c]) / inv_std3[c]) * 255.0f)
+ *                                     torchvision's Normalize (sub_, div_) then ToPILImage (mul(255).byte()),
+ *                                     misc.py:240-245, 326-329; inv_mean3 / inv_std3 are 3 HOST floats each, the fp32
+ *                                     values the reference forms from -mean/std and 1/std; three fp32 operations each
+ *                                     rounded on its own, a true IEEE division, no FMA
+ *     gt_rgb[p]   = palette[gts[p] & 255]    the low 8 bits as in astype(np.uint8)      colorize_mask(..).convert('RGB'),
+ *     pred_rgb[p] = palette[pred[p]]                                                      misc.py:333-341
+ *     comp_rgb[p][c] = u8(a + alpha * (b - a)),  a = input_rgb[p][c],  b = pred_rgb[p][c]
+ *                                     Image.blend(input, prediction, alpha), misc.py:342: the subtraction, the product
+ *                                     and the sum each rounded to fp32, no FMA
+ *     label_ids[p] = id_table[pred[p]]        the train-id -> label-id loop of misc.py:318-322 as one table
+ *     prob_u8[p]   = u8(prob[p] * 255.0f)     misc.py:314, 377-378
+ *     err_u8[p]    = (err[p] * 255) & 255     misc.py:377-378 on the 0/1 error mask
+ * Outside [0, 256) the reference's float -> byte cast is undefined behaviour; HERE u8 SATURATES (v <= 0 -> 0,
+ * v >= 255 -> 255) and NaN gives 0.
+ * image fp32 [3][H][W] with plane stride plane_stride >= H*W elements; gts int64 [H][W]; pred, err uint8 [H][W]; prob
+ * fp32 [H][W]; palette 256 x 3 bytes and id_table 256 bytes on the DEVICE; the *_rgb outputs uint8 [H][W][3], the
+ * others uint8 [H][W].  Every input and output is optional; an output is written when it is given.  SSA_EINVAL (before
+ * the device is touched) when no output is given, when an output lacks an input it is made from (input_rgb: image,
+ * inv_mean3, inv_std3; gt_rgb: gts, palette; pred_rgb: pred, palette; comp_rgb: those of input_rgb and pred_rgb and
+ * 0 <= alpha <= 1; label_ids: pred, id_table; prob_u8: prob; err_u8: err) and for H < 1 || W < 1.  Pointers on the grid
+ * of their wide access (image, gts, prob 16 bytes with plane_stride % 4 == 0; everything else 4 bytes) take the wide
+ * path, four pixels per thread and step; any other alignment is served pixel by pixel with the same result.       */
+int ssa_dump_tail(const float* image, long plane_stride, const float* inv_mean3, const float* inv_std3,
+                  const int64_t* gts, const unsigned char* pred, const unsigned char* palette,
+                  const unsigned char* id_table, const float* prob, const unsigned char* err, float alpha,
+                  int H, int W, unsigned char* input_rgb, unsigned char* gt_rgb, unsigned char* pred_rgb,
+                  unsigned char* comp_rgb, unsigned char* label_ids, unsigned char* prob_u8, unsigned char* err_u8,
+                  void* stream);
+
+/* out[i] = u8(mask[i] * 255.0f) over n fp32 values, u8 as above (saturating, NaN -> 0): the attn_* assets of
+ * ImageDumper.dump (misc.py:373-378), which live at sizes of their own.  SSA_EINVAL for a null pointer or n < 1.   */
+int ssa_mask_u8(const float* mask, long n, unsigned char* out, void* stream);
+
 /* Optimizer step (train.py:509 on the torch.optim.SGD of loss/optimizer.py:47-53;
  * SURVEY.md 8f rank 3): for every tensor i, elementwise in fp32
  *     d = g + weight_decay*p;  buf = momentum*buf + d;  p -= lr * (nesterov ? d + momentum*buf : buf)

@@ -239,6 +239,9 @@ _SIGS = {
     "ssa_confusion_matrix": ([_P, c_int, _P, c_long, c_int, _P, _P, _P], c_int),
     "ssa_eval_tail": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P,
                        _P, _P], c_int),
+    "ssa_dump_tail": ([_P, c_long, POINTER(c_float), POINTER(c_float), _P, _P, _P, _P, _P, _P, c_float, c_int, c_int,
+                       _P, _P, _P, _P, _P, _P, _P, _P], c_int),
+    "ssa_mask_u8": ([_P, c_long, _P, _P], c_int),
     "ssa_sgd_momentum_step": ([_P, _P, _P, _P, c_int, c_float, _P, c_float, c_float, c_int, _P, _P], c_int),
     "ssa_amp_check_grads": ([_P, _P, c_int, _P, _P], c_int),
     "ssa_amp_update": ([_P, c_int, c_float, c_float, c_float, c_float, _P], c_int),

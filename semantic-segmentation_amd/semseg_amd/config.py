@@ -50,7 +50,12 @@ def _defaults():
         CLASS_UNIFORM_BIAS=None,     # config.py:253: per-class multipliers of the per-class item count, or None
         CENTROID_ROOT="/home/dcg-adlr-atao-data.cosmos277/assets/uniform_centroids",   # config.py:52, 82-83
         TRANSLATE_AUG_FIX=False,     # config.py:112 (--translate_aug_fix, config.py:266-267)
+        MEAN=[0.485, 0.456, 0.406],  # config.py:96-97: what ImageDumper de-normalises with (utils/dumper.py)
+        STD=[0.229, 0.224, 0.225],
     )
+    c.DATASET_INST = None            # config.py:381 (update_dataset_inst): colorize_mask / id_to_trainid of ImageDumper
+    c.RESULT_DIR = None              # config.py:64, 298 (args.result_dir): where ImageDumper writes
+    c.GLOBAL_RANK = 0                # config.py:49, 358: only rank 0 dumps images
     c.OPTIONS = AttrDict(INIT_DECODER=False)
     c.EPOCH = 0                      # config.py:50 (train.py sets it every epoch)
     c.BATCH_WEIGHTING = False        # config.py:55 (class weights over the batch instead of per image)
@@ -77,7 +82,11 @@ def sync_from_reference(ref_cfg):
         cfg.LOSS[k] = getattr(ref_cfg.LOSS, k)
     cfg.DATASET.NUM_CLASSES = ref_cfg.DATASET.NUM_CLASSES
     cfg.DATASET.IGNORE_LABEL = ref_cfg.DATASET.IGNORE_LABEL
-    for k in ("NAME", "CLASS_UNIFORM_PCT", "CLASS_UNIFORM_TILE", "CLASS_UNIFORM_BIAS", "CENTROID_ROOT", "TRANSLATE_AUG_FIX"):
+    for k in ("DATASET_INST", "RESULT_DIR", "GLOBAL_RANK"):
+        if hasattr(ref_cfg, k):
+            cfg[k] = getattr(ref_cfg, k)
+    for k in ("NAME", "CLASS_UNIFORM_PCT", "CLASS_UNIFORM_TILE", "CLASS_UNIFORM_BIAS", "CENTROID_ROOT", "TRANSLATE_AUG_FIX",
+              "MEAN", "STD"):
         if hasattr(ref_cfg.DATASET, k):         # (CLASS_UNIFORM_BIAS exists only after assert_and_infer_cfg)
             cfg.DATASET[k] = getattr(ref_cfg.DATASET, k)
     cfg.DROPOUT_COARSE_BOOST_CLASSES = getattr(ref_cfg, "DROPOUT_COARSE_BOOST_CLASSES", None)

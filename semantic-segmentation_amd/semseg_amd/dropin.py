@@ -14,6 +14,8 @@ time, so `train.py`, `config.py` and `scripts/*.yml` run unchanged:
   utils.trnval_utils (eval_minibatch, flip_tensor, resize_tensor; validate_topn raises) -- only with
   install(device_eval_tail=True)
         -> semseg_amd.utils.eval_tail    (train.py:44; the evaluation tail in one kernel instead of on the host)
+  utils.misc.ImageDumper -- only with install(device_dumper=True)
+        -> semseg_amd.utils.dumper.ImageDumper   (train.py:43; the per-pixel work of dump() in one kernel)
   apex.parallel.SyncBatchNorm / DistributedDataParallel, apex.amp
         -> semseg_amd.nn.SyncBatchNorm / semseg_amd.parallel.DistributedDataParallel /
            semseg_amd.amp behind apex.amp's names: `--fp16` selects the fp16-storage build of the library and
@@ -77,9 +79,13 @@ def _select_storage_from_argv():
         os.environ["SSA_ACT_DTYPE"] = "fp16"
 
 
-def install(replace_apex=True, device_eval_tail=False):
+def install(replace_apex=True, device_eval_tail=False, device_dumper=False):
     """device_eval_tail=True also registers `utils.trnval_utils` (train.py:44 imports eval_minibatch and validate_topn
-    from there): eval_minibatch with its tail on the device (semseg_amd/utils/eval_tail.py).  Off by default."""
+    from there): eval_minibatch with its tail on the device (semseg_amd/utils/eval_tail.py).  Off by default.
+    device_dumper=True (off by default; implies device_eval_tail) puts semseg_amd.utils.dumper.ImageDumper where
+    train.py:43 imports the class from -- the attribute `ImageDumper` of the reference's own `utils.misc`, which is
+    imported for that and keeps everything else it holds -- and makes the registered eval_minibatch leave its assets
+    on the device (assets_on_device=True), where that class picks them up."""
     _select_storage_from_argv()
     from . import nn as snn, parallel, network, loss
     from .network import ocrnet, hrnetv2, ocr_utils, utils as nutils, mynn, deepv3, mscale, mscale2, attnscale
@@ -111,7 +117,7 @@ def install(replace_apex=True, device_eval_tail=False):
                       ("network.mscale2", mscale2), ("network.attnscale", attnscale),
                       ("loss.utils", criteria), ("loss.rmi", criteria), ("loss.optimizer", optimizer)):
         sys.modules[name] = mod
-    if device_eval_tail:
+    if device_eval_tail or device_dumper:
         import importlib
         et = importlib.import_module(__package__ + ".utils.eval_tail")     # (the package re-exports a function of that name)
         tv = types.ModuleType("utils.trnval_utils")
@@ -119,6 +125,10 @@ def install(replace_apex=True, device_eval_tail=False):
         for fname in ("eval_minibatch", "flip_tensor", "resize_tensor", "validate_topn"):
             setattr(tv, fname, getattr(et, fname))
         et._SYNC_CFG[0] = True
+        if device_dumper:
+            tv.eval_minibatch = functools.partial(et.eval_minibatch, assets_on_device=True)
+            from .utils import dumper
+            importlib.import_module("utils.misc").ImageDumper = dumper.ImageDumper
         sys.modules["utils.trnval_utils"] = tv
     return network, loss
 

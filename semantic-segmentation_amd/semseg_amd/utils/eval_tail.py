@@ -158,7 +158,7 @@ def _to_host(tensors):
     return outs
 
 
-def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx):
+def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx, assets_on_device=False):
     """utils/trnval_utils.py:82-198 with its tail on the device.  Same arguments, same returns: (assets, _iou_acc) with
     `predictions` int64 ndarray [B,H,W], `prob_mask` CPU fp32 tensor, `err_mask` int ndarray (calc_metrics), every
     `pred_*` of the last pass as int64 ndarray at its own size, every `attn_*` passed through, `_iou_acc` int64 [C,C];
@@ -166,7 +166,10 @@ def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx):
     are flipped / resized there; every pass's prediction (resized to the input size where its scale is not 1) is a
     source of ONE ssa_eval_tail.  What comes back per batch: uint8 predictions and error mask, the fp32 probability,
     C x C counters and two doubles, in one synchronisation.  The loss rides in the same launch when `criterion` is this
-    package's CrossEntropyLoss2d with the dataset's ignore label; any other criterion is called on the averaged tensor."""
+    package's CrossEntropyLoss2d with the dataset's ignore label; any other criterion is called on the averaged tensor.
+    assets_on_device=True (what `dropin.install(device_dumper=True)` passes): the assets stay where the tail wrote them,
+    for utils/dumper.py -- `predictions`, `err_mask` and every `pred_*` as device uint8, `prob_mask` as device fp32, the
+    `attn_*` untouched, and the uploaded batch under `input_images` / `gt_images`; only the counters come back."""
     from ..config import cfg
     from ..loss.criteria import CrossEntropyLoss2d
     if _SYNC_CFG[0] and "config" in sys.modules and hasattr(sys.modules["config"], "assert_and_infer_cfg"):
@@ -217,6 +220,20 @@ def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx):
             if "pred_" in item:
                 names.append(item)
                 extra.append(eval_tail([t], [0], t.shape[1], want=("pred",)).pred)
+        if assets_on_device:
+            host = _to_host([res.hist] + ([res.loss_acc] if fused else []))
+            if fused:
+                loss = _mean_loss(host[1])
+            if calc_metrics:
+                val_loss.update(loss, batch_pixel_size)
+            extra_d = dict(zip(names, extra))
+            assets = {item: extra_d.get(item, output_dict[item]) for item in output_dict
+                      if "attn_" in item or "pred_" in item}
+            assets["predictions"], assets["prob_mask"] = res.pred, res.prob
+            if calc_metrics:
+                assets["err_mask"] = res.err
+            assets["input_images"], assets["gt_images"] = images, gts
+            return assets, host[0].numpy().astype(np.int64)
         dev_out = [res.pred, res.prob, res.hist] + ([res.err] if calc_metrics else []) + ([res.loss_acc] if fused else [])
         host = _to_host(dev_out + extra)
     pred_h, prob_h, hist_h = host[0], host[1], host[2]
