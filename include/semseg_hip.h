@@ -479,10 +479,15 @@ int ssa_nchw_f32_to_nhwc_bf16(const float* x, void* y, int B, int C, int H, int 
  * [B,Ho,Wo,cpad]; Ho==Hi && Wo==Wi is an exact copy.                          */
 int ssa_image_resize_to_nhwc_bf16(const float* x, int B, int C, int Hi, int Wi,
                                   void* y, int Ho, int Wo, int cpad, void* stream);
+/* The same under either index rule of ResizeX (network/mynn.py:15 reads cfg.MODEL.ALIGN_CORNERS, the reference's
+ * --align_corners): align_corners 0 is the entry point above, 1 is ATen's align_corners=True rule (scale =
+ * (in - 1) / (out - 1), s = scale * o); any other value is SSA_EINVAL.            */
+int ssa_image_resize_to_nhwc(const float* x, int B, int C, int Hi, int Wi,
+                             void* y, int Ho, int Wo, int cpad, int align_corners, void* stream);
 
 /* -------------------------------------------------------------- bilinear ----
  * F.interpolate(mode='bilinear', align_corners=False): network/mynn.py:42-114,
- * network/hrnetv2.py:246-249,440-445 (K8).  in_dtype/out_dtype: 0 bf16, 1 f32.
+ * network/hrnetv2.py:246-249,440-445 (K8; align_corners=True: the ssa_resize_* entry points below).  in_dtype/out_dtype: 0 bf16, 1 f32.
  * Backward is a deterministic gather (no atomics).                             */
 int ssa_bilinear_fwd(const void* x, int in_dtype, int B, int Hi, int Wi, int C,
                      int ldx, void* y, int out_dtype, int Ho, int Wo, int ldy,
@@ -498,6 +503,26 @@ int ssa_bilinear_bwd_x(const void* dy, int dy_dtype, int B, int Ho, int Wo, int 
                        void* stream);
 int ssa_bilinear_bwd_y(const float* tmp, int B, int Ho, int Wi, int C, void* dx, int dx_dtype, int Hi, int lddx,
                        void* stream);
+/* The four entry points above under either index rule: F.interpolate(mode='bilinear', align_corners=
+ * cfg.MODEL.ALIGN_CORNERS) -- the reference's --align_corners, read by network/mynn.py:15 (Upsample, Upsample2, scale_as,
+ * ResizeX, DownX), network/hrnetv2.py:27, network/ocr_utils.py:117 and utils/trnval_utils.py:54.  align_corners 0: the
+ * entry points above, bit for bit (they are calls of these with 0).  align_corners 1: ATen's rule, every step one fp32
+ * operation: scale = out > 1 ? (in - 1) / (out - 1) : 0, s = scale * o, i0 = min((int)s, in - 1), i1 = i0 + (i0 < in - 1),
+ * l1 = s - i0, l0 = 1 - l1.  scale == 0 (out == 1 or in == 1): every output reads input 0, whose gradient is the sum
+ * of all output gradients.  An input pixel receives from up to ceil(2 / scale) outputs per axis (9 at 64 -> 256, 17 at
+ * 128 -> 1024).  Same dtype routing, same refusals; align_corners outside {0, 1} is SSA_EINVAL.                     */
+int ssa_resize_bilinear_fwd(const void* x, int in_dtype, int B, int Hi, int Wi, int C,
+                            int ldx, void* y, int out_dtype, int Ho, int Wo, int ldy,
+                            int align_corners, void* stream);
+int ssa_resize_bilinear_bwd(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C,
+                            int lddy, void* dx, int dx_dtype, int Hi, int Wi, int lddx,
+                            int align_corners, void* stream);
+/* The separable pair (network/mynn.py:42-114, network/hrnetv2.py:246-249,440-445): pass X and pass Y of one resize take
+ * the same align_corners.  Two dependent launches: never both in one ssa_group bracket.                              */
+int ssa_resize_bilinear_bwd_x(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, float* tmp, int Wi,
+                              int align_corners, void* stream);
+int ssa_resize_bilinear_bwd_y(const float* tmp, int B, int Ho, int Wi, int C, void* dx, int dx_dtype, int Hi, int lddx,
+                              int align_corners, void* stream);
 
 /* ----------------------------------------------------------------- pooling ----
  * DeepLabV3+/ResNet-50 (BASELINE configs[0]): nn.MaxPool2d(3, 2, 1) of the ResNet

@@ -1,8 +1,11 @@
-// Bilinear resampling, align_corners=False, on NHWC tensors.
-// Same index arithmetic as ATen's upsample_bilinear2d (fp32 source index,
-// negative source clamped to 0, i1 = i0 + (i0 < in-1)), which is what
-// F.interpolate does behind network/mynn.py:42-114 and
-// network/hrnetv2.py:246-249,440-445.
+// Bilinear resampling on NHWC tensors, under both index rules of F.interpolate: align_corners=False and
+// align_corners=True (cfg.MODEL.ALIGN_CORNERS, the reference's --align_corners).  The rule is a compile-time
+// parameter (AC) of every body: the AC = false instantiations are the code they were before the second rule existed.
+// Same index arithmetic as ATen's upsample_bilinear2d (fp32 source index; align_corners=False: scale = in / out,
+// s = scale * (o + 0.5) - 0.5, negative source clamped to 0; align_corners=True: scale = (in - 1) / (out - 1), 0 for
+// out == 1, s = scale * o; both: i1 = i0 + (i0 < in-1)), which is what F.interpolate does behind
+// network/mynn.py:15,42-114, network/hrnetv2.py:27,246-249,440-445, network/ocr_utils.py:117 and
+// utils/trnval_utils.py:54.
 // The backward is a gather over the output pixels that reference an input
 // pixel -- deterministic, no atomics.
 #include <type_traits>
@@ -14,9 +17,27 @@ namespace {
 
 struct Src { int i0, i1; float l0, l1; };
 
+template <bool AC>
 __device__ __forceinline__ Src src_index(int o, float scale, int in_size) {
-  float s = scale * ((float)o + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
+  float s;
+  if constexpr (AC) {
+    // Every step ONE fp32 operation, as in ATen: the product is rounded before l1 = s - i0 uses it.  Left to the
+    // compiler, scale * o - i0 becomes one fused multiply-add on the unrounded product, and l1 moves by up to half a unit
+    // in the last place of s -- times a gradient window that is 1e-5 of the result, outside the arithmetic bound of the
+    // tests (measured on the device: 6 x the bound at 33 -> 67).  Contraction is off for this block only.
+#pragma clang fp contract(off)
+    s = scale * (float)o;                 // no half-pixel shift, never negative
+    Src r;
+    r.i0 = (int)s;
+    if (r.i0 > in_size - 1) r.i0 = in_size - 1;
+    r.i1 = r.i0 + (r.i0 < in_size - 1 ? 1 : 0);
+    r.l1 = s - (float)r.i0;
+    r.l0 = 1.f - r.l1;
+    return r;
+  } else {
+    s = scale * ((float)o + 0.5f) - 0.5f;
+    s = s < 0.f ? 0.f : s;
+  }
   Src r;
   r.i0 = (int)s;
   if (r.i0 > in_size - 1) r.i0 = in_size - 1;
@@ -27,6 +48,7 @@ __device__ __forceinline__ Src src_index(int o, float scale, int in_size) {
 }
 
 // ---- forward, 8 bf16 channels per thread
+template <bool AC>
 __device__ __forceinline__ void bilinear_fwd_v8_body(const bf16_t* __restrict__ x, int B, int Hi, int Wi, int C, int ldx,
                                 bf16_t* __restrict__ y, int Ho, int Wo, int ldy, float sh, float sw, const int bx, const int gx) {
   const int VC = C >> 3;
@@ -37,7 +59,7 @@ __device__ __forceinline__ void bilinear_fwd_v8_body(const bf16_t* __restrict__ 
     const int ox = (int)(t % Wo); t /= Wo;
     const int oy = (int)(t % Ho);
     const int b = (int)(t / Ho);
-    const Src ys = src_index(oy, sh, Hi), xs = src_index(ox, sw, Wi);
+    const Src ys = src_index<AC>(oy, sh, Hi), xs = src_index<AC>(ox, sw, Wi);
     const bf16_t* base = x + (long)b * Hi * Wi * ldx + cg * 8;
     float v00[8], v01[8], v10[8], v11[8], o[8];
     unpack8(*reinterpret_cast<const uint4*>(base + ((long)ys.i0 * Wi + xs.i0) * ldx), v00);
@@ -52,7 +74,7 @@ __device__ __forceinline__ void bilinear_fwd_v8_body(const bf16_t* __restrict__ 
 }
 
 // ---- forward, one element per thread (any C, any dtype pair)
-template <typename InT, typename OutT>
+template <typename InT, typename OutT, bool AC>
 __device__ __forceinline__ void bilinear_fwd_s_body(const InT* __restrict__ x, int B, int Hi, int Wi, int C, int ldx,
                                OutT* __restrict__ y, int Ho, int Wo, int ldy, float sh, float sw, const int bx, const int gx) {
   const long n = (long)B * Ho * Wo * C;
@@ -62,7 +84,7 @@ __device__ __forceinline__ void bilinear_fwd_s_body(const InT* __restrict__ x, i
     const int ox = (int)(t % Wo); t /= Wo;
     const int oy = (int)(t % Ho);
     const int b = (int)(t / Ho);
-    const Src ys = src_index(oy, sh, Hi), xs = src_index(ox, sw, Wi);
+    const Src ys = src_index<AC>(oy, sh, Hi), xs = src_index<AC>(ox, sw, Wi);
     const InT* base = x + (long)b * Hi * Wi * ldx + c;
     const float v00 = ld_as_f32(base + ((long)ys.i0 * Wi + xs.i0) * ldx);
     const float v01 = ld_as_f32(base + ((long)ys.i0 * Wi + xs.i1) * ldx);
@@ -76,15 +98,36 @@ __device__ __forceinline__ void bilinear_fwd_s_body(const InT* __restrict__ x, i
 constexpr int kMaxCand = 12;      // candidate columns whose weights the gather kernels keep in registers
 
 // candidate output range that can reference input index i
+// align_corners=True: input i carries weight for the outputs with s = scale * o in the OPEN interval (i - 1, i + 1), i.e.
+// (i - 1) / scale < o < (i + 1) / scale.  The bounds computed here -- one reciprocal, one product -- lie within
+// o * 3 * 2^-24 of the bounds the forward's fp32 product implies, below 1 for o < 2^22, so floor / ceil of them enclose
+// every such output (an end point itself carries weight 0; sizes from 2^20 get one more candidate per side); up to
+// ceil(2 / scale) + 2 candidates.  scale == 0 (out == 1 or in == 1): every output reads input 0, so input 0 gets the
+// whole axis and every other input the single candidate 0, whose weight for it is 0 (never an empty range: the batched
+// loads re-read the window's last column).
+template <bool AC>
 __device__ __forceinline__ void cand_range(int i, float scale, int out_size, int* lo, int* hi) {
+  if constexpr (AC) {
+    if (scale == 0.f) { *lo = 0; *hi = i == 0 ? out_size - 1 : 0; return; }
+    const float inv = 1.f / scale;
+    const int pad = out_size >> 20 ? 1 : 0;
+    int a = (int)floorf(((float)i - 1.f) * inv) - pad;
+    int b = (int)ceilf(((float)i + 1.f) * inv) + pad;
+    a = a < 0 ? 0 : a;
+    b = b > out_size - 1 ? out_size - 1 : b;
+    *lo = a < b ? a : b;                  // (a beyond the last output: only the last one is a candidate)
+    *hi = b;
+    return;
+  }
   const float inv = 1.f / scale;
   int a = (int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1;
   int b = (int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1;
   *lo = a < 0 ? 0 : a;
   *hi = b > out_size - 1 ? out_size - 1 : b;
 }
+template <bool AC>
 __device__ __forceinline__ float weight_for(int o, float scale, int in_size, int i) {
-  const Src s = src_index(o, scale, in_size);
+  const Src s = src_index<AC>(o, scale, in_size);
   float w = 0.f;
   if (s.i0 == i) w += s.l0;
   if (s.i1 == i) w += s.l1;
@@ -92,15 +135,17 @@ __device__ __forceinline__ float weight_for(int o, float scale, int in_size, int
 }
 
 // the candidates of an input index that really carry weight
+template <bool AC>
 __device__ __forceinline__ void tight_range(int i, float scale, int out_size, int in_size, int* lo, int* hi) {
   int a, b;
-  cand_range(i, scale, out_size, &a, &b);
-  while (a < b && weight_for(a, scale, in_size, i) == 0.f) ++a;
-  while (b > a && weight_for(b, scale, in_size, i) == 0.f) --b;
+  cand_range<AC>(i, scale, out_size, &a, &b);
+  while (a < b && weight_for<AC>(a, scale, in_size, i) == 0.f) ++a;
+  while (b > a && weight_for<AC>(b, scale, in_size, i) == 0.f) --b;
   *lo = a; *hi = b;
 }
 
 // ---- backward gather, 8 bf16 channels per thread
+template <bool AC>
 __device__ __forceinline__ void bilinear_bwd_v8_body(const bf16_t* __restrict__ dy, int B, int Ho, int Wo, int C,
                                 int lddy, bf16_t* __restrict__ dx, int Hi, int Wi, int lddx, float sh,
                                 float sw, const int bx, const int gx) {
@@ -113,8 +158,8 @@ __device__ __forceinline__ void bilinear_bwd_v8_body(const bf16_t* __restrict__ 
     const int iy = (int)(t % Hi);
     const int b = (int)(t / Hi);
     int ylo, yhi, xlo, xhi;
-    cand_range(iy, sh, Ho, &ylo, &yhi);
-    cand_range(ix, sw, Wo, &xlo, &xhi);
+    cand_range<AC>(iy, sh, Ho, &ylo, &yhi);
+    cand_range<AC>(ix, sw, Wo, &xlo, &xhi);
     float acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = 0.f;
@@ -125,9 +170,9 @@ __device__ __forceinline__ void bilinear_bwd_v8_body(const bf16_t* __restrict__ 
     const int nx = xhi - xlo + 1;
     const bool hoisted = nx <= kMaxCand;
 #pragma unroll
-    for (int k = 0; k < kMaxCand; ++k) wxs[k] = (hoisted && k < nx) ? weight_for(xlo + k, sw, Wi, ix) : 0.f;
+    for (int k = 0; k < kMaxCand; ++k) wxs[k] = (hoisted && k < nx) ? weight_for<AC>(xlo + k, sw, Wi, ix) : 0.f;
     for (int oy = ylo; oy <= yhi; ++oy) {
-      const float wy = weight_for(oy, sh, Hi, iy);
+      const float wy = weight_for<AC>(oy, sh, Hi, iy);
       if (wy == 0.f) continue;
       const bf16_t* row = base + (long)oy * Wo * lddy;
       if (hoisted) {
@@ -142,7 +187,7 @@ __device__ __forceinline__ void bilinear_bwd_v8_body(const bf16_t* __restrict__ 
         }
       } else {
         for (int ox = xlo; ox <= xhi; ++ox) {
-          const float wx = weight_for(ox, sw, Wi, ix);
+          const float wx = weight_for<AC>(ox, sw, Wi, ix);
           if (wx == 0.f) continue;
           float g[8];
           unpack8(*reinterpret_cast<const uint4*>(row + (long)ox * lddy), g);
@@ -156,7 +201,7 @@ __device__ __forceinline__ void bilinear_bwd_v8_body(const bf16_t* __restrict__ 
   }
 }
 
-template <typename InT, typename OutT>
+template <typename InT, typename OutT, bool AC>
 __device__ __forceinline__ void bilinear_bwd_s_body(const InT* __restrict__ dy, int B, int Ho, int Wo, int C, int lddy,
                                OutT* __restrict__ dx, int Hi, int Wi, int lddx, float sh, float sw, const int bx, const int gx) {
   const long n = (long)B * Hi * Wi * C;
@@ -167,17 +212,17 @@ __device__ __forceinline__ void bilinear_bwd_s_body(const InT* __restrict__ dy, 
     const int iy = (int)(t % Hi);
     const int b = (int)(t / Hi);
     int ylo, yhi, xlo, xhi;
-    cand_range(iy, sh, Ho, &ylo, &yhi);
-    cand_range(ix, sw, Wo, &xlo, &xhi);
+    cand_range<AC>(iy, sh, Ho, &ylo, &yhi);
+    cand_range<AC>(ix, sw, Wo, &xlo, &xhi);
     float acc = 0.f;
     const InT* base = dy + (long)b * Ho * Wo * lddy + c;
     float wxs[kMaxCand];
     const int nx = xhi - xlo + 1;
     const bool hoisted = nx <= kMaxCand;
 #pragma unroll
-    for (int k = 0; k < kMaxCand; ++k) wxs[k] = (hoisted && k < nx) ? weight_for(xlo + k, sw, Wi, ix) : 0.f;
+    for (int k = 0; k < kMaxCand; ++k) wxs[k] = (hoisted && k < nx) ? weight_for<AC>(xlo + k, sw, Wi, ix) : 0.f;
     for (int oy = ylo; oy <= yhi; ++oy) {
-      const float wy = weight_for(oy, sh, Hi, iy);
+      const float wy = weight_for<AC>(oy, sh, Hi, iy);
       if (wy == 0.f) continue;
       const InT* row = base + (long)oy * Wo * lddy;
       if (hoisted) {
@@ -186,7 +231,7 @@ __device__ __forceinline__ void bilinear_bwd_s_body(const InT* __restrict__ dy, 
           if (wxs[k] != 0.f) acc += wy * wxs[k] * ld_as_f32(row + (long)(xlo + k) * lddy);
       } else {
         for (int ox = xlo; ox <= xhi; ++ox) {
-          const float wx = weight_for(ox, sw, Wi, ix);
+          const float wx = weight_for<AC>(ox, sw, Wi, ix);
           if (wx == 0.f) continue;
           acc += wy * wx * ld_as_f32(row + (long)ox * lddy);
         }
@@ -207,7 +252,7 @@ __device__ __forceinline__ void bilinear_bwd_s_body(const InT* __restrict__ dy, 
 constexpr int kXRows = 1;         // output rows per thread of pass X (8, with the column weights computed once for all of them,
                                   // measured slower: 34 -> 46 us per launch, too few threads in flight; profiles/r04_notes.md call I)
 
-template <typename InT, int V>
+template <typename InT, int V, bool AC>
 __device__ __forceinline__ void bilinear_bwd_x_body(const InT* __restrict__ dy, int B, int Ho, int Wo, int C, int lddy,
                                                     float* __restrict__ tmp, int Wi, float sw, const int bx, const int gx) {
   const int VC = C / V;
@@ -224,7 +269,7 @@ __device__ __forceinline__ void bilinear_bwd_x_body(const InT* __restrict__ dy, 
     // between the candidates' loads they were issued one at a time (profiles/r06_notes.md, call U: the same change made
     // the few-channel fp32 form 2.3x faster)
     int xlo, xhi;
-    tight_range(ix, sw, Wo, Wi, &xlo, &xhi);
+    tight_range<AC>(ix, sw, Wo, Wi, &xlo, &xhi);
     const int nx = xhi - xlo + 1;
     for (int rr = 0; rr < kXRows; ++rr) {
       const long r = r0 + rr;
@@ -239,7 +284,7 @@ __device__ __forceinline__ void bilinear_bwd_x_body(const InT* __restrict__ dy, 
         long off[T];
 #pragma unroll
         for (int k = 0; k < T; ++k) {
-          w[k] = k < nx ? weight_for(xlo + k, sw, Wi, ix) : 0.f;
+          w[k] = k < nx ? weight_for<AC>(xlo + k, sw, Wi, ix) : 0.f;
           off[k] = (long)(xlo + (k < nx ? k : nx - 1)) * lddy;
         }
         if constexpr (V == 8) {
@@ -267,7 +312,7 @@ __device__ __forceinline__ void bilinear_bwd_x_body(const InT* __restrict__ dy, 
         batch(std::integral_constant<int, 8>());
       } else {
         for (int ox = xlo; ox <= xhi; ++ox) {
-          const float wx = weight_for(ox, sw, Wi, ix);
+          const float wx = weight_for<AC>(ox, sw, Wi, ix);
           if (wx == 0.f) continue;
           if constexpr (V == 8) {
             float g[8];
@@ -290,7 +335,7 @@ __device__ __forceinline__ void bilinear_bwd_x_body(const InT* __restrict__ dy, 
   }
 }
 
-template <typename OutT, int V>
+template <typename OutT, int V, bool AC>
 __device__ __forceinline__ void bilinear_bwd_y_body(const float* __restrict__ tmp, int B, int Ho, int Wi, int C,
                                                     OutT* __restrict__ dx, int Hi, int lddx, float sh, const int bx,
                                                     const int gx) {
@@ -303,7 +348,7 @@ __device__ __forceinline__ void bilinear_bwd_y_body(const float* __restrict__ tm
     const int iy = (int)(t % Hi);
     const int b = (int)(t / Hi);
     int ylo, yhi;
-    tight_range(iy, sh, Ho, Hi, &ylo, &yhi);
+    tight_range<AC>(iy, sh, Ho, Hi, &ylo, &yhi);
     const int ny = yhi - ylo + 1;
     float acc[V];
 #pragma unroll
@@ -315,7 +360,7 @@ __device__ __forceinline__ void bilinear_bwd_y_body(const float* __restrict__ tm
       const float* src[T];
 #pragma unroll
       for (int k = 0; k < T; ++k) {
-        w[k] = k < ny ? weight_for(ylo + k, sh, Hi, iy) : 0.f;
+        w[k] = k < ny ? weight_for<AC>(ylo + k, sh, Hi, iy) : 0.f;
         src[k] = col + (long)(ylo + (k < ny ? k : ny - 1)) * Wi * C;
       }
       if constexpr (V == 8) {
@@ -341,7 +386,7 @@ __device__ __forceinline__ void bilinear_bwd_y_body(const float* __restrict__ tm
       batch(std::integral_constant<int, 8>());
     } else {
       for (int oy = ylo; oy <= yhi; ++oy) {
-        const float wy = weight_for(oy, sh, Hi, iy);
+        const float wy = weight_for<AC>(oy, sh, Hi, iy);
         if (wy == 0.f) continue;
         const float* src = col + (long)oy * Wi * C;
         if constexpr (V == 8) {
@@ -364,6 +409,7 @@ __device__ __forceinline__ void bilinear_bwd_y_body(const float* __restrict__ tm
 
 // NCHW fp32 image -> (optionally resized) NHWC bf16, channels zero padded.
 // ResizeX(x, s) of network/mynn.py:101-114 fused with the layout change.
+template <bool AC>
 __global__ void image_resize_kernel(const float* __restrict__ x, int B, int C, int Hi, int Wi,
                                     bf16_t* __restrict__ y, int Ho, int Wo, int cpad, float sh,
                                     float sw) {
@@ -373,7 +419,7 @@ __global__ void image_resize_kernel(const float* __restrict__ x, int B, int C, i
     const int ox = (int)(t % Wo); t /= Wo;
     const int oy = (int)(t % Ho);
     const int b = (int)(t / Ho);
-    const Src ys = src_index(oy, sh, Hi), xs = src_index(ox, sw, Wi);
+    const Src ys = src_index<AC>(oy, sh, Hi), xs = src_index<AC>(ox, sw, Wi);
     bf16_t* dst = y + i * cpad;
     for (int c0 = 0; c0 < cpad; c0 += 8) {
       float f[8];
@@ -421,40 +467,40 @@ __global__ void resize_nearest_u8_kernel(const unsigned char* __restrict__ src, 
 
 
 // ---- group-aware wrappers (group.h)
-template <typename InT, typename OutT, bool V8, bool BWD>
+template <typename InT, typename OutT, bool V8, bool BWD, bool AC>
 struct BilinearK {
   // forward: (x [B,Hi,Wi,C] ldx) -> (y [B,Ho,Wo,C] ldy); backward: (dy [B,Ho,Wo,C]) -> (dx [B,Hi,Wi,C])
   struct Args { const InT* src; OutT* dst; int B, Hs, Ws, C, lds, Hd, Wd, ldd; float sh, sw; };
   static constexpr int NT = 256;
   static __device__ __forceinline__ void run(const Args& a, int bx, int, int gx) {
-    if constexpr (V8 && !BWD) bilinear_fwd_v8_body(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
-    else if constexpr (V8 && BWD) bilinear_bwd_v8_body(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
-    else if constexpr (!BWD) bilinear_fwd_s_body<InT, OutT>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
-    else bilinear_bwd_s_body<InT, OutT>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
+    if constexpr (V8 && !BWD) bilinear_fwd_v8_body<AC>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
+    else if constexpr (V8 && BWD) bilinear_bwd_v8_body<AC>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
+    else if constexpr (!BWD) bilinear_fwd_s_body<InT, OutT, AC>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
+    else bilinear_bwd_s_body<InT, OutT, AC>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.ldd, a.sh, a.sw, bx, gx);
   }
 };
-template <typename InT, typename OutT, bool V8, bool BWD>
+template <typename InT, typename OutT, bool V8, bool BWD, bool AC>
 int launch_bilinear(const void* src, int B, int Hs, int Ws, int C, int lds, void* dst, int Hd, int Wd, int ldd,
                     float sh, float sw, long nthreads, hipStream_t s) {
-  typedef BilinearK<InT, OutT, V8, BWD> K;
+  typedef BilinearK<InT, OutT, V8, BWD, AC> K;
   typename K::Args a{(const InT*)src, (OutT*)dst, B, Hs, Ws, C, lds, Hd, Wd, ldd, sh, sw};
   return ssa::submit<K>(a, grid_for(nthreads), 1, 0, s);
 }
 
-template <typename InT, int V>
+template <typename InT, int V, bool AC>
 struct BilinearBwdXK {
   struct Args { const InT* dy; float* tmp; int B, Ho, Wo, C, lddy, Wi; float sw; };
   static constexpr int NT = 256;
   static __device__ __forceinline__ void run(const Args& a, int bx, int, int gx) {
-    bilinear_bwd_x_body<InT, V>(a.dy, a.B, a.Ho, a.Wo, a.C, a.lddy, a.tmp, a.Wi, a.sw, bx, gx);
+    bilinear_bwd_x_body<InT, V, AC>(a.dy, a.B, a.Ho, a.Wo, a.C, a.lddy, a.tmp, a.Wi, a.sw, bx, gx);
   }
 };
-template <typename OutT, int V>
+template <typename OutT, int V, bool AC>
 struct BilinearBwdYK {
   struct Args { const float* tmp; OutT* dx; int B, Ho, Wi, C, Hi, lddx; float sh; };
   static constexpr int NT = 256;
   static __device__ __forceinline__ void run(const Args& a, int bx, int, int gx) {
-    bilinear_bwd_y_body<OutT, V>(a.tmp, a.B, a.Ho, a.Wi, a.C, a.dx, a.Hi, a.lddx, a.sh, bx, gx);
+    bilinear_bwd_y_body<OutT, V, AC>(a.tmp, a.B, a.Ho, a.Wi, a.C, a.dx, a.Hi, a.lddx, a.sh, bx, gx);
   }
 };
 
@@ -464,7 +510,7 @@ struct BilinearBwdYK {
 // ([pixel][C], odd C = conflict free) and writes it with unit stride.
 constexpr int kPxMaxC = 32;      // LDS tile [256][C] stays below 32 KB
 
-template <typename InT, typename OutT>
+template <typename InT, typename OutT, bool AC>
 __device__ __forceinline__ void bilinear_fwd_px_body(const InT* __restrict__ x, int B, int Hi, int Wi, int C, int ldx,
                                                      OutT* __restrict__ y, int Ho, int Wo, float sh, float sw,
                                                      const int bx, const int gx) {
@@ -477,7 +523,7 @@ __device__ __forceinline__ void bilinear_fwd_px_body(const InT* __restrict__ x, 
       const int ox = p % Wo;
       const int t = p / Wo;
       const int oy = t % Ho, b = t / Ho;
-      const Src ys = src_index(oy, sh, Hi), xs = src_index(ox, sw, Wi);
+      const Src ys = src_index<AC>(oy, sh, Hi), xs = src_index<AC>(ox, sw, Wi);
       const InT* r0 = x + ((long)(b * Hi + ys.i0) * Wi) * ldx;
       const InT* r1 = x + ((long)(b * Hi + ys.i1) * Wi) * ldx;
       const InT* p00 = r0 + (long)xs.i0 * ldx;
@@ -511,7 +557,7 @@ __device__ __forceinline__ void bilinear_fwd_px_body(const InT* __restrict__ x, 
 // into LDS.  Summation order differs from the gather (x first): fp32 rounding only.
 constexpr int kTileX = 16;
 
-template <typename OutT, int TY, int TAPS>
+template <typename OutT, int TY, int TAPS, bool AC>
 __device__ __forceinline__ void bilinear_bwd_tile_body(const float* __restrict__ dy, int B, int Ho, int Wo, int C, int lddy,
                                                        OutT* __restrict__ dx, int Hi, int Wi, int lddx, float sh, float sw,
                                                        const int maxrows, const int bx, const int gx) {
@@ -536,19 +582,19 @@ __device__ __forceinline__ void bilinear_bwd_tile_body(const float* __restrict__
     if (tid < kTileX) {
       const int ix = tx0 + tid;
       int lo = 0, hi = -1;
-      if (ix < Wi) tight_range(ix, sw, Wo, Wi, &lo, &hi);
+      if (ix < Wi) tight_range<AC>(ix, sw, Wo, Wi, &lo, &hi);
       int n = hi - lo + 1;
       if (n > TAPS) n = TAPS;              // (never: the host picks TAPS >= the widest window of the scale)
       xlo[tid] = lo; nxs[tid] = n < 0 ? 0 : n;
-      for (int k = 0; k < kMaxCand; ++k) wxs[tid * kMaxCand + k] = k < n ? weight_for(lo + k, sw, Wi, ix) : 0.f;
+      for (int k = 0; k < kMaxCand; ++k) wxs[tid * kMaxCand + k] = k < n ? weight_for<AC>(lo + k, sw, Wi, ix) : 0.f;
     } else if (tid >= 64 && tid < 64 + TY) {
       const int j = tid - 64, iy = ty0 + j;
       int lo = 0, hi = -1;
-      if (iy < Hi) tight_range(iy, sh, Ho, Hi, &lo, &hi);
+      if (iy < Hi) tight_range<AC>(iy, sh, Ho, Hi, &lo, &hi);
       int n = hi - lo + 1;
       if (n > TAPS) n = TAPS;
       ylo[j] = lo; nys[j] = n < 0 ? 0 : n;
-      for (int k = 0; k < kMaxCand; ++k) wys[j * kMaxCand + k] = k < n ? weight_for(lo + k, sh, Hi, iy) : 0.f;
+      for (int k = 0; k < kMaxCand; ++k) wys[j * kMaxCand + k] = k < n ? weight_for<AC>(lo + k, sh, Hi, iy) : 0.f;
     }
     __syncthreads();
     const int r0 = ylo[0];
@@ -610,54 +656,80 @@ __device__ __forceinline__ void bilinear_bwd_tile_body(const float* __restrict__
   }
 }
 
-template <typename OutT, int TY, int TAPS>
+template <typename OutT, int TY, int TAPS, bool AC>
 struct BilinearBwdTileK {
   struct Args { const float* dy; OutT* dx; int B, Ho, Wo, C, lddy, Hi, Wi, lddx; float sh, sw; int maxrows; };
   static constexpr int NT = 256;
   static __device__ __forceinline__ void run(const Args& a, int bx, int, int gx) {
-    bilinear_bwd_tile_body<OutT, TY, TAPS>(a.dy, a.B, a.Ho, a.Wo, a.C, a.lddy, a.dx, a.Hi, a.Wi, a.lddx, a.sh, a.sw, a.maxrows, bx, gx);
+    bilinear_bwd_tile_body<OutT, TY, TAPS, AC>(a.dy, a.B, a.Ho, a.Wo, a.C, a.lddy, a.dx, a.Hi, a.Wi, a.lddx, a.sh, a.sw, a.maxrows, bx, gx);
   }
 };
 // gradient rows / columns an input pixel can receive from: ceil(2 / scale) + 1 covers the two-tap footprint's inverse
 static int bwd_window(float scale) { return (int)ceilf(2.f / scale) + 1; }
 static int bwd_tile_rows(float sh, int TY) { return (int)ceilf((float)(TY + 1) / sh) + 2; }
-static size_t bwd_tile_lds(float sh, int TY, int C) {
-  return sizeof(float) * ((kTileX + TY) * kMaxCand + 2 * (kTileX + TY) + (size_t)bwd_tile_rows(sh, TY) * kTileX * C);
-}
 // taps the widest window of a scale has: 2 f for an integer upsampling factor f (what the tight ranges come to), else
 // the inverse footprint's bound
 static int bwd_taps(float scale) {
   const float f = 1.f / scale;
   return f == floorf(f) ? 2 * (int)f : bwd_window(scale);
 }
-template <typename OutT, int TY, int TAPS>
+// ---- the same three for align_corners=True (scale = (in - 1) / (out - 1), s = scale * o)
+// An input pixel i receives from the outputs with s in the open interval (i - 1, i + 1): an interval of length
+// 2 / scale in o, which holds at most ceil(2 / scale) integers -- 9 at 64 -> 256 (scale 63/255) where the other rule
+// has 8, 17 at 128 -> 1024.  The device decides with the fp32 product scale * o, which moves each end by less than
+// o * 2^-22: one more tap allows for it.  scale == 0 (out == 1 or in == 1): input 0 receives from the whole axis.
+static int bwd_window_ac(float scale, int out_size) {
+  if (scale == 0.f) return out_size;
+  const float w = ceilf(2.f / scale) + 1.f;
+  return w < (float)out_size ? (int)w : out_size;
+}
+static int bwd_taps_ac(float scale, int out_size) { return bwd_window_ac(scale, out_size); }
+// rows a tile of TY input rows receives from: s in (ty0 - 1, ty0 + TY), an interval of length (TY + 1) / scale in o, at
+// most ceil((TY + 1) / scale) integers and one for the fp32 product; never more than the axis has
+static int bwd_tile_rows_ac(float sh, int TY, int Ho) {
+  if (sh == 0.f) return Ho;
+  const float r = ceilf((float)(TY + 1) / sh) + 1.f;
+  return r < (float)Ho ? (int)r : Ho;
+}
+template <bool AC>
+static int tile_rows(float sh, int TY, int Ho) { return AC ? bwd_tile_rows_ac(sh, TY, Ho) : bwd_tile_rows(sh, TY); }
+template <bool AC>
+static int tile_taps(float scale, int out_size) { return AC ? bwd_taps_ac(scale, out_size) : bwd_taps(scale); }
+template <bool AC>
+static size_t bwd_tile_lds(float sh, int TY, int C, int Ho) {
+  return sizeof(float) * ((kTileX + TY) * kMaxCand + 2 * (kTileX + TY) + (size_t)tile_rows<AC>(sh, TY, Ho) * kTileX * C);
+}
+template <typename OutT, int TY, int TAPS, bool AC>
 int launch_bilinear_bwd_tile(const void* dy, int B, int Ho, int Wo, int C, int lddy, void* dx, int Hi, int Wi, int lddx,
                              float sh, float sw, hipStream_t s) {
-  typedef BilinearBwdTileK<OutT, TY, TAPS> K;
-  typename K::Args a{(const float*)dy, (OutT*)dx, B, Ho, Wo, C, lddy, Hi, Wi, lddx, sh, sw, bwd_tile_rows(sh, TY)};
+  typedef BilinearBwdTileK<OutT, TY, TAPS, AC> K;
+  typename K::Args a{(const float*)dy, (OutT*)dx, B, Ho, Wo, C, lddy, Hi, Wi, lddx, sh, sw, tile_rows<AC>(sh, TY, Ho)};
   const long ntiles = (long)B * ((Hi + TY - 1) / TY) * ((Wi + kTileX - 1) / kTileX);
-  return ssa::submit<K>(a, (int)(ntiles > 16384 ? 16384 : ntiles), 1, bwd_tile_lds(sh, TY, C), s);
+  return ssa::submit<K>(a, (int)(ntiles > 16384 ? 16384 : ntiles), 1, bwd_tile_lds<AC>(sh, TY, C, Ho), s);
 }
 // routed here: fp32 gradient of an upsampling resize, few channels, windows that fit the weight tables and the LDS rows
+// (align_corners=True: the same refusals with its own tap counts -- 2x has 5 or 6, 4x has 9 or 10, 8x has 17 and more: refused)
+template <bool AC>
 static bool bwd_tile_ok(int B, int Ho, int Wo, int Hi, int Wi, int C, float sh, float sw, int TY) {
   if (C < 8 || C > kPxMaxC || sh > 1.f || sw > 1.f) return false;       // (one channel: 16 of 256 lanes busy -- the gather)
-  if (bwd_taps(sw) > kMaxCand || bwd_taps(sh) > kMaxCand) return false;
-  if (bwd_tile_lds(sh, TY, C) > 60 * 1024) return false;
+  if (AC && (Ho < Hi || Wo < Wi)) return false;                         // (scale 0 of an axis reduced to one pixel is no upsampling)
+  if (tile_taps<AC>(sw, Wo) > kMaxCand || tile_taps<AC>(sh, Ho) > kMaxCand) return false;
+  if (bwd_tile_lds<AC>(sh, TY, C, Ho) > 60 * 1024) return false;
   return (long)B * Ho * Wo < (1L << 30);
 }
 
-template <typename InT, typename OutT>
+template <typename InT, typename OutT, bool AC>
 struct BilinearPxK {
   struct Args { const InT* src; OutT* dst; int B, Hs, Ws, C, lds, Hd, Wd, ldd; float sh, sw; };
   static constexpr int NT = 256;
   static __device__ __forceinline__ void run(const Args& a, int bx, int, int gx) {
-    bilinear_fwd_px_body<InT, OutT>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.sh, a.sw, bx, gx);
+    bilinear_fwd_px_body<InT, OutT, AC>(a.src, a.B, a.Hs, a.Ws, a.C, a.lds, a.dst, a.Hd, a.Wd, a.sh, a.sw, bx, gx);
   }
 };
-template <typename InT, typename OutT>
+template <typename InT, typename OutT, bool AC>
 int launch_bilinear_px(const void* src, int B, int Hs, int Ws, int C, int lds, void* dst, int Hd, int Wd, int ldd,
                        float sh, float sw, hipStream_t s) {
-  typedef BilinearPxK<InT, OutT> K;
+  typedef BilinearPxK<InT, OutT, AC> K;
   typename K::Args a{(const InT*)src, (OutT*)dst, B, Hs, Ws, C, lds, Hd, Wd, ldd, sh, sw};
   const long npix = (long)B * Hd * Wd;
   return ssa::submit<K>(a, grid_for(npix), 1, (size_t)256 * C * sizeof(float), s);
@@ -667,118 +739,189 @@ static bool px_ok(int B, int Hs, int Ws, int Hd, int Wd, int C, int ldd) {
   return C <= kPxMaxC && ldd == C && (long)B * Hs * Ws < (1L << 30) && (long)B * Hd * Wd < (1L << 30);
 }
 
-}  // namespace
+// the scale of an axis: (in / out) under align_corners=False; ATen's area_pixel_compute_scale under align_corners=True
+template <bool AC>
+inline float axis_scale(int n_in, int n_out) {
+  if (AC) return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
+  return (float)n_in / (float)n_out;
+}
 
-extern "C" {
-
-int ssa_bilinear_fwd(const void* x, int in_dtype, int B, int Hi, int Wi, int C, int ldx, void* y,
-                     int out_dtype, int Ho, int Wo, int ldy, void* stream) {
-  if (!x || !y || B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return SSA_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
+template <bool AC>
+int resize_fwd(const void* x, int in_dtype, int B, int Hi, int Wi, int C, int ldx, void* y, int out_dtype, int Ho, int Wo,
+               int ldy, hipStream_t s) {
+  const float sh = axis_scale<AC>(Hi, Ho), sw = axis_scale<AC>(Wi, Wo);
   const long n = (long)B * Ho * Wo * C;
   if (in_dtype == 0 && out_dtype == 0 && C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0)
-    return launch_bilinear<bf16_t, bf16_t, true, false>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n / 8, s);
+    return launch_bilinear<bf16_t, bf16_t, true, false, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n / 8, s);
   if (px_ok(B, Hi, Wi, Ho, Wo, C, ldy)) {
-    if (in_dtype == 1 && out_dtype == 1) return launch_bilinear_px<float, float>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, s);
-    if (in_dtype == 0 && out_dtype == 1) return launch_bilinear_px<bf16_t, float>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, s);
+    if (in_dtype == 1 && out_dtype == 1) return launch_bilinear_px<float, float, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, s);
+    if (in_dtype == 0 && out_dtype == 1) return launch_bilinear_px<bf16_t, float, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, s);
   }
   if (in_dtype == 0 && out_dtype == 0)
-    return launch_bilinear<bf16_t, bf16_t, false, false>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
+    return launch_bilinear<bf16_t, bf16_t, false, false, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
   if (in_dtype == 0 && out_dtype == 1)
-    return launch_bilinear<bf16_t, float, false, false>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
+    return launch_bilinear<bf16_t, float, false, false, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
   if (in_dtype == 1 && out_dtype == 1)
-    return launch_bilinear<float, float, false, false>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
+    return launch_bilinear<float, float, false, false, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
   if (in_dtype == 1 && out_dtype == 0)
-    return launch_bilinear<float, bf16_t, false, false>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
+    return launch_bilinear<float, bf16_t, false, false, AC>(x, B, Hi, Wi, C, ldx, y, Ho, Wo, ldy, sh, sw, n, s);
   return SSA_EINVAL;
 }
 
-int ssa_bilinear_bwd(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, void* dx,
-                     int dx_dtype, int Hi, int Wi, int lddx, void* stream) {
-  if (!dy || !dx || B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return SSA_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
+template <bool AC>
+int resize_bwd(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, void* dx, int dx_dtype, int Hi, int Wi,
+               int lddx, hipStream_t s) {
+  const float sh = axis_scale<AC>(Hi, Ho), sw = axis_scale<AC>(Wi, Wo);
   const long n = (long)B * Hi * Wi * C;
   if (dy_dtype == 0 && dx_dtype == 0 && C % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0)
-    return launch_bilinear<bf16_t, bf16_t, true, true>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n / 8, s);
+    return launch_bilinear<bf16_t, bf16_t, true, true, AC>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n / 8, s);
   // (a per-pixel gather for the few-channel fp32 tensors was measured 4x SLOWER than the per-element
   // kernel -- lanes = pixels read with a 76-byte stride -- and is not used; profiles/r02_notes.md)
   // few-channel fp32 gradient of an upsampling resize: the LDS-tiled separable kernel (one launch)
   static const bool tiled = [] { const char* e = getenv("SSA_BILINEAR_BWD_TILE"); return !(e && e[0] == '0'); }();
-  if (tiled && dy_dtype == 1 && bwd_tile_ok(B, Ho, Wo, Hi, Wi, C, sh, sw, 4)) {
-    const int taps = bwd_taps(sw) > bwd_taps(sh) ? bwd_taps(sw) : bwd_taps(sh);
-#define SSA_BWD_TILE(T, N) launch_bilinear_bwd_tile<T, 4, N>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, s)
+  if (tiled && dy_dtype == 1 && bwd_tile_ok<AC>(B, Ho, Wo, Hi, Wi, C, sh, sw, 4)) {
+    const int tw = tile_taps<AC>(sw, Wo), th = tile_taps<AC>(sh, Ho);
+    const int taps = tw > th ? tw : th;
+#define SSA_BWD_TILE(T, N) launch_bilinear_bwd_tile<T, 4, N, AC>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, s)
     if (dx_dtype == 1) return taps <= 4 ? SSA_BWD_TILE(float, 4) : taps <= 8 ? SSA_BWD_TILE(float, 8) : SSA_BWD_TILE(float, 12);
     return taps <= 4 ? SSA_BWD_TILE(bf16_t, 4) : taps <= 8 ? SSA_BWD_TILE(bf16_t, 8) : SSA_BWD_TILE(bf16_t, 12);
 #undef SSA_BWD_TILE
   }
   if (dy_dtype == 1 && dx_dtype == 1)
-    return launch_bilinear<float, float, false, true>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n, s);
+    return launch_bilinear<float, float, false, true, AC>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n, s);
   if (dy_dtype == 1 && dx_dtype == 0)
-    return launch_bilinear<float, bf16_t, false, true>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n, s);
+    return launch_bilinear<float, bf16_t, false, true, AC>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n, s);
   if (dy_dtype == 0 && dx_dtype == 0)
-    return launch_bilinear<bf16_t, bf16_t, false, true>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n, s);
+    return launch_bilinear<bf16_t, bf16_t, false, true, AC>(dy, B, Ho, Wo, C, lddy, dx, Hi, Wi, lddx, sh, sw, n, s);
   return SSA_EINVAL;
+}
+
+template <bool AC>
+int resize_bwd_x(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, float* tmp, int Wi, hipStream_t s) {
+  const float sw = axis_scale<AC>(Wi, Wo);
+  const long n = (long)B * Ho * Wi * C;
+  if (dy_dtype == 0 && C % 8 == 0 && lddy % 8 == 0 && (reinterpret_cast<uintptr_t>(dy) & 15u) == 0) {
+    typedef BilinearBwdXK<bf16_t, 8, AC> K;
+    typename K::Args a{(const bf16_t*)dy, tmp, B, Ho, Wo, C, lddy, Wi, sw};
+    return ssa::submit<K>(a, grid_for(n / 8 / kXRows + 1), 1, 0, s);
+  }
+  if (dy_dtype == 0) {
+    typedef BilinearBwdXK<bf16_t, 1, AC> K;
+    typename K::Args a{(const bf16_t*)dy, tmp, B, Ho, Wo, C, lddy, Wi, sw};
+    return ssa::submit<K>(a, grid_for(n / kXRows + 1), 1, 0, s);
+  }
+  if (dy_dtype == 1) {
+    typedef BilinearBwdXK<float, 1, AC> K;
+    typename K::Args a{(const float*)dy, tmp, B, Ho, Wo, C, lddy, Wi, sw};
+    return ssa::submit<K>(a, grid_for(n / kXRows + 1), 1, 0, s);
+  }
+  return SSA_EINVAL;
+}
+
+template <bool AC>
+int resize_bwd_y(const float* tmp, int B, int Ho, int Wi, int C, void* dx, int dx_dtype, int Hi, int lddx, hipStream_t s) {
+  const float sh = axis_scale<AC>(Hi, Ho);
+  const long n = (long)B * Hi * Wi * C;
+  if (dx_dtype == 0 && C % 8 == 0 && lddx % 8 == 0 && ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(tmp)) & 15u) == 0) {
+    typedef BilinearBwdYK<bf16_t, 8, AC> K;
+    typename K::Args a{tmp, (bf16_t*)dx, B, Ho, Wi, C, Hi, lddx, sh};
+    return ssa::submit<K>(a, grid_for(n / 8), 1, 0, s);
+  }
+  if (dx_dtype == 0) {
+    typedef BilinearBwdYK<bf16_t, 1, AC> K;
+    typename K::Args a{tmp, (bf16_t*)dx, B, Ho, Wi, C, Hi, lddx, sh};
+    return ssa::submit<K>(a, grid_for(n), 1, 0, s);
+  }
+  if (dx_dtype == 1) {
+    typedef BilinearBwdYK<float, 1, AC> K;
+    typename K::Args a{tmp, (float*)dx, B, Ho, Wi, C, Hi, lddx, sh};
+    return ssa::submit<K>(a, grid_for(n), 1, 0, s);
+  }
+  return SSA_EINVAL;
+}
+
+template <bool AC>
+int image_resize(const float* x, int B, int C, int Hi, int Wi, void* y, int Ho, int Wo, int cpad, hipStream_t s) {
+  const float sh = axis_scale<AC>(Hi, Ho), sw = axis_scale<AC>(Wi, Wo);
+  hipLaunchKernelGGL(image_resize_kernel<AC>, dim3(grid_for((long)B * Ho * Wo)), dim3(256), 0, s, x, B, C, Hi, Wi,
+                     (bf16_t*)y, Ho, Wo, cpad, sh, sw);
+  SSA_LAUNCH_CHECK();
+  return SSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssa_resize_bilinear_fwd(const void* x, int in_dtype, int B, int Hi, int Wi, int C, int ldx, void* y,
+                            int out_dtype, int Ho, int Wo, int ldy, int align_corners, void* stream) {
+  if (!x || !y || B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return SSA_EINVAL;
+  if (align_corners != 0 && align_corners != 1) return SSA_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return align_corners ? resize_fwd<true>(x, in_dtype, B, Hi, Wi, C, ldx, y, out_dtype, Ho, Wo, ldy, s)
+                       : resize_fwd<false>(x, in_dtype, B, Hi, Wi, C, ldx, y, out_dtype, Ho, Wo, ldy, s);
+}
+
+int ssa_bilinear_fwd(const void* x, int in_dtype, int B, int Hi, int Wi, int C, int ldx, void* y,
+                     int out_dtype, int Ho, int Wo, int ldy, void* stream) {
+  return ssa_resize_bilinear_fwd(x, in_dtype, B, Hi, Wi, C, ldx, y, out_dtype, Ho, Wo, ldy, 0, stream);
+}
+
+int ssa_resize_bilinear_bwd(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, void* dx,
+                            int dx_dtype, int Hi, int Wi, int lddx, int align_corners, void* stream) {
+  if (!dy || !dx || B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return SSA_EINVAL;
+  if (align_corners != 0 && align_corners != 1) return SSA_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return align_corners ? resize_bwd<true>(dy, dy_dtype, B, Ho, Wo, C, lddy, dx, dx_dtype, Hi, Wi, lddx, s)
+                       : resize_bwd<false>(dy, dy_dtype, B, Ho, Wo, C, lddy, dx, dx_dtype, Hi, Wi, lddx, s);
+}
+
+int ssa_bilinear_bwd(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, void* dx,
+                     int dx_dtype, int Hi, int Wi, int lddx, void* stream) {
+  return ssa_resize_bilinear_bwd(dy, dy_dtype, B, Ho, Wo, C, lddy, dx, dx_dtype, Hi, Wi, lddx, 0, stream);
+}
+
+int ssa_resize_bilinear_bwd_x(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, float* tmp, int Wi,
+                              int align_corners, void* stream) {
+  if (!dy || !tmp || B <= 0 || Ho <= 0 || Wo <= 0 || Wi <= 0 || C <= 0) return SSA_EINVAL;
+  if (reinterpret_cast<uintptr_t>(tmp) & 15u) return SSA_EINVAL;
+  if (align_corners != 0 && align_corners != 1) return SSA_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return align_corners ? resize_bwd_x<true>(dy, dy_dtype, B, Ho, Wo, C, lddy, tmp, Wi, s)
+                       : resize_bwd_x<false>(dy, dy_dtype, B, Ho, Wo, C, lddy, tmp, Wi, s);
 }
 
 int ssa_bilinear_bwd_x(const void* dy, int dy_dtype, int B, int Ho, int Wo, int C, int lddy, float* tmp, int Wi,
                        void* stream) {
-  if (!dy || !tmp || B <= 0 || Ho <= 0 || Wo <= 0 || Wi <= 0 || C <= 0) return SSA_EINVAL;
-  if (reinterpret_cast<uintptr_t>(tmp) & 15u) return SSA_EINVAL;
+  return ssa_resize_bilinear_bwd_x(dy, dy_dtype, B, Ho, Wo, C, lddy, tmp, Wi, 0, stream);
+}
+
+int ssa_resize_bilinear_bwd_y(const float* tmp, int B, int Ho, int Wi, int C, void* dx, int dx_dtype, int Hi, int lddx,
+                              int align_corners, void* stream) {
+  if (!tmp || !dx || B <= 0 || Ho <= 0 || Hi <= 0 || Wi <= 0 || C <= 0) return SSA_EINVAL;
+  if (align_corners != 0 && align_corners != 1) return SSA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const float sw = (float)Wi / (float)Wo;
-  const long n = (long)B * Ho * Wi * C;
-  if (dy_dtype == 0 && C % 8 == 0 && lddy % 8 == 0 && (reinterpret_cast<uintptr_t>(dy) & 15u) == 0) {
-    typedef BilinearBwdXK<bf16_t, 8> K;
-    K::Args a{(const bf16_t*)dy, tmp, B, Ho, Wo, C, lddy, Wi, sw};
-    return ssa::submit<K>(a, grid_for(n / 8 / kXRows + 1), 1, 0, s);
-  }
-  if (dy_dtype == 0) {
-    typedef BilinearBwdXK<bf16_t, 1> K;
-    K::Args a{(const bf16_t*)dy, tmp, B, Ho, Wo, C, lddy, Wi, sw};
-    return ssa::submit<K>(a, grid_for(n / kXRows + 1), 1, 0, s);
-  }
-  if (dy_dtype == 1) {
-    typedef BilinearBwdXK<float, 1> K;
-    K::Args a{(const float*)dy, tmp, B, Ho, Wo, C, lddy, Wi, sw};
-    return ssa::submit<K>(a, grid_for(n / kXRows + 1), 1, 0, s);
-  }
-  return SSA_EINVAL;
+  return align_corners ? resize_bwd_y<true>(tmp, B, Ho, Wi, C, dx, dx_dtype, Hi, lddx, s)
+                       : resize_bwd_y<false>(tmp, B, Ho, Wi, C, dx, dx_dtype, Hi, lddx, s);
 }
 
 int ssa_bilinear_bwd_y(const float* tmp, int B, int Ho, int Wi, int C, void* dx, int dx_dtype, int Hi, int lddx,
                        void* stream) {
-  if (!tmp || !dx || B <= 0 || Ho <= 0 || Hi <= 0 || Wi <= 0 || C <= 0) return SSA_EINVAL;
+  return ssa_resize_bilinear_bwd_y(tmp, B, Ho, Wi, C, dx, dx_dtype, Hi, lddx, 0, stream);
+}
+
+int ssa_image_resize_to_nhwc(const float* x, int B, int C, int Hi, int Wi, void* y, int Ho, int Wo, int cpad,
+                             int align_corners, void* stream) {
+  if (!x || !y || cpad % 8 || cpad < C || Ho <= 0 || Wo <= 0) return SSA_EINVAL;
+  if (align_corners != 0 && align_corners != 1) return SSA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const float sh = (float)Hi / (float)Ho;
-  const long n = (long)B * Hi * Wi * C;
-  if (dx_dtype == 0 && C % 8 == 0 && lddx % 8 == 0 && ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(tmp)) & 15u) == 0) {
-    typedef BilinearBwdYK<bf16_t, 8> K;
-    K::Args a{tmp, (bf16_t*)dx, B, Ho, Wi, C, Hi, lddx, sh};
-    return ssa::submit<K>(a, grid_for(n / 8), 1, 0, s);
-  }
-  if (dx_dtype == 0) {
-    typedef BilinearBwdYK<bf16_t, 1> K;
-    K::Args a{tmp, (bf16_t*)dx, B, Ho, Wi, C, Hi, lddx, sh};
-    return ssa::submit<K>(a, grid_for(n), 1, 0, s);
-  }
-  if (dx_dtype == 1) {
-    typedef BilinearBwdYK<float, 1> K;
-    K::Args a{tmp, (float*)dx, B, Ho, Wi, C, Hi, lddx, sh};
-    return ssa::submit<K>(a, grid_for(n), 1, 0, s);
-  }
-  return SSA_EINVAL;
+  return align_corners ? image_resize<true>(x, B, C, Hi, Wi, y, Ho, Wo, cpad, s)
+                       : image_resize<false>(x, B, C, Hi, Wi, y, Ho, Wo, cpad, s);
 }
 
 int ssa_image_resize_to_nhwc_bf16(const float* x, int B, int C, int Hi, int Wi, void* y, int Ho,
                                   int Wo, int cpad, void* stream) {
-  if (!x || !y || cpad % 8 || cpad < C || Ho <= 0 || Wo <= 0) return SSA_EINVAL;
-  const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
-  hipLaunchKernelGGL(image_resize_kernel, dim3(grid_for((long)B * Ho * Wo)), dim3(256), 0,
-                     (hipStream_t)stream, x, B, C, Hi, Wi, (bf16_t*)y, Ho, Wo, cpad, sh, sw);
-  SSA_LAUNCH_CHECK();
-  return SSA_OK;
+  return ssa_image_resize_to_nhwc(x, B, C, Hi, Wi, y, Ho, Wo, cpad, 0, stream);
 }
 
 int ssa_resize_nearest_u8(const unsigned char* src, int B, int Hs, int Ws, unsigned char* dst, int Hd,

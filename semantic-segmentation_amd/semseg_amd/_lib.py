@@ -173,6 +173,14 @@ _SIGS = {
                           c_int, _P], c_int),
     "ssa_bilinear_bwd_x": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P], c_int),
     "ssa_bilinear_bwd_y": ([_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P], c_int),
+    # the same five with `int align_corners` in front of the stream (cfg.MODEL.ALIGN_CORNERS)
+    "ssa_image_resize_to_nhwc": ([_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P], c_int),
+    "ssa_resize_bilinear_fwd": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int,
+                                 c_int, c_int, _P], c_int),
+    "ssa_resize_bilinear_bwd": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int,
+                                 c_int, c_int, _P], c_int),
+    "ssa_resize_bilinear_bwd_x": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P], c_int),
+    "ssa_resize_bilinear_bwd_y": ([_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P], c_int),
     "ssa_maxpool3x3s2_fwd": ([_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P], c_int),
     "ssa_maxpool3x3s2_bwd": ([_P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P], c_int),
     "ssa_dwconv3x3": ([POINTER(DwConvDesc), _P, _P, _P, _P, _P, c_int, _P], c_int),

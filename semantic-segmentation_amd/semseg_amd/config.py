@@ -96,6 +96,5 @@ def sync_from_reference(ref_cfg):
     cfg.BATCH_WEIGHTING = getattr(ref_cfg, "BATCH_WEIGHTING", False)
     cfg.BORDER_WINDOW = getattr(ref_cfg, "BORDER_WINDOW", 1)
     cfg.STRICTBORDERCLASS = getattr(ref_cfg, "STRICTBORDERCLASS", None)
-    assert not cfg.MODEL.ALIGN_CORNERS, "only align_corners=False is implemented"
     for k in ("MSCALE_OLDARCH", "MSCALE_DROPOUT", "MSCALE_CAT_SCALE_FLT"):      # config.py:132-135
         assert not getattr(m, k, False), "cfg.MODEL.%s is not on the accelerated path" % k

@@ -29,6 +29,10 @@ activation pools); further signatures, and every step after a capture that raise
 sequence eagerly.  With N > 1 every rank must see the same shapes in the same iteration (the warm-up steps of a
 capture issue collectives).  Reloading the optimizer's state (`optim.load_state_dict`) drops the captured graphs:
 they hold the addresses of the old state tensors (momentum buffers, moment estimates, step records).
+
+cfg.MODEL.ALIGN_CORNERS is a launch argument of every bilinear resize, read from cfg when the resize is called: a
+captured step or forward has the value of its capture baked in.  Changing the flag afterwards does not reach the
+graphs; drop them with `invalidate()` -- the reference fixes the flag at import anyway.
 """
 import collections
 import os

@@ -1935,8 +1935,9 @@ def _dt(t):
     raise TypeError(t.dtype)
 
 
-def _bilinear_bwd_group(jobs):
-    """Backward of N bilinear resizes.  job = (dy_ptr, dy_dtype_code, lddy, B, Hi, Wi, C, Ho, Wo, dx).  Upsampling
+def _bilinear_bwd_group(jobs, align_corners=False):
+    """Backward of N bilinear resizes under one index rule (align_corners: the rule their forward ran with).
+    job = (dy_ptr, dy_dtype_code, lddy, B, Hi, Wi, C, Ho, Wo, dx).  Upsampling
     resizes (Ho >= 2 Hi and Wo >= 2 Wi) of 16-bit tensors with C % 8 == 0 -- the trunk's branch upsamples, 2x / 4x /
     8x -- run the separable form: all X passes of the level in one bracket, all Y passes in the next
     (ssa_bilinear_bwd_x / _y; 607 -> 275 us per step).  The others take the one-pass gather: for the 19-channel fp32
@@ -1947,8 +1948,11 @@ def _bilinear_bwd_group(jobs):
     those (fp32, 8..32 channels, upsampling) to ONE LDS-tiled launch -- both separable passes inside a 4 x 16-pixel input
     tile, the row pass with all of a thread's loads in flight (4 rows x 4 / 8 / 12 taps, no branch between them): 73 -> 32
     us at 256^2 <- 1024^2, 87 -> 45 us at 512^2 <- 1024^2 (profiles/r06_bilinbench.txt), -0.27 ms per step; the earlier
-    forms lost because their loops ran one load at a time."""
+    forms lost because their loops ran one load at a time.
+    align_corners=True: the route policy below (separable when Ho >= 2 Hi and Wo >= 2 Wi) is carried over UNMEASURED
+    from the other rule; its windows are wider (5-6 taps at 2x, 9-10 at 4x, 17 at 8x), which the policy does not know."""
     L = lib()
+    ac = int(bool(align_corners))
 
     def separable(j):
         return j[1] == 0 and j[6] % 8 == 0 and j[2] % 8 == 0 and j[7] >= 2 * j[4] and j[8] >= 2 * j[5]
@@ -1959,31 +1963,36 @@ def _bilinear_bwd_group(jobs):
         for dyp, dt, lddy, B, Hi, Wi, C, Ho, Wo, dx in sep:
             tmp = torch.empty((B, Ho, Wi, C), dtype=torch.float32, device=dx.device)
             tmps.append(tmp)
-            check(L.ssa_bilinear_bwd_x(dyp, dt, B, Ho, Wo, C, lddy, _p(tmp), Wi, _s()), "ssa_bilinear_bwd_x")
+            check(L.ssa_resize_bilinear_bwd_x(dyp, dt, B, Ho, Wo, C, lddy, _p(tmp), Wi, ac, _s()), "ssa_resize_bilinear_bwd_x")
         for dyp, dt, lddy, B, Hi, Wi, C, Ho, Wo, dx in rest:
-            check(L.ssa_bilinear_bwd(dyp, dt, B, Ho, Wo, C, lddy, _p(dx), _dt(dx), Hi, Wi, C, _s()), "ssa_bilinear_bwd")
+            check(L.ssa_resize_bilinear_bwd(dyp, dt, B, Ho, Wo, C, lddy, _p(dx), _dt(dx), Hi, Wi, C, ac, _s()),
+                  "ssa_resize_bilinear_bwd")
     if sep:
         with group():
             for (dyp, dt, lddy, B, Hi, Wi, C, Ho, Wo, dx), tmp in zip(sep, tmps):
-                check(L.ssa_bilinear_bwd_y(_p(tmp), B, Ho, Wi, C, _p(dx), _dt(dx), Hi, C, _s()), "ssa_bilinear_bwd_y")
+                check(L.ssa_resize_bilinear_bwd_y(_p(tmp), B, Ho, Wi, C, _p(dx), _dt(dx), Hi, C, ac, _s()),
+                      "ssa_resize_bilinear_bwd_y")
 
 
-class BilinearGroupFn(torch.autograd.Function):
-    """F.interpolate(mode='bilinear', align_corners=False) of N tensors; spec[i] = (Ho, Wo, out_f32)."""
+class _BilinearGroupFn(torch.autograd.Function):
+    """F.interpolate(mode='bilinear', align_corners=align_corners) of N tensors; spec[i] = (Ho, Wo, out_f32).  The
+    flag is kept in ctx: a backward runs under its forward's rule, whatever cfg.MODEL.ALIGN_CORNERS says by then."""
 
     @staticmethod
-    def forward(ctx, spec, *xs):
+    def forward(ctx, spec, align_corners, *xs):
+        ac = int(bool(align_corners))
         prep = [_pixels(x) for x in xs]
         ys, meta = [], []
         with group():
             for (x, ldx), (Ho, Wo, out_f32) in zip(prep, spec):
                 B, Hi, Wi, C = x.shape
                 y = torch.empty((B, Ho, Wo, C), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-                check(lib().ssa_bilinear_fwd(_p(x), _dt(x), B, Hi, Wi, C, ldx, _p(y), _dt(y), Ho, Wo, C, _s()),
-                      "ssa_bilinear_fwd")
+                check(lib().ssa_resize_bilinear_fwd(_p(x), _dt(x), B, Hi, Wi, C, ldx, _p(y), _dt(y), Ho, Wo, C, ac, _s()),
+                      "ssa_resize_bilinear_fwd")
                 ys.append(y)
                 meta.append((B, Hi, Wi, C, Ho, Wo, x.dtype))
         ctx.meta = meta
+        ctx.align_corners = bool(ac)
         return tuple(ys)
 
     @staticmethod
@@ -1997,7 +2006,7 @@ class BilinearGroupFn(torch.autograd.Function):
             if dy.dtype == ACT_DTYPE and (lddy % 8 or dy.data_ptr() % 16):
                 dy, lddy = dy.contiguous(), C
             prep.append((dy, lddy))
-        dxs = [None]
+        dxs = [None, None]
         jobs = []
         for pr, (B, Hi, Wi, C, Ho, Wo, in_dtype) in zip(prep, ctx.meta):
             if pr is None:
@@ -2007,19 +2016,28 @@ class BilinearGroupFn(torch.autograd.Function):
             dx = torch.empty((B, Hi, Wi, C), dtype=in_dtype, device=dy.device)
             jobs.append((_p(dy), _dt(dy), lddy, B, Hi, Wi, C, Ho, Wo, dx))
             dxs.append(dx)
-        _bilinear_bwd_group(jobs)
+        _bilinear_bwd_group(jobs, ctx.align_corners)
         return tuple(dxs)
 
 
-class UpsampleCatGroupFn(torch.autograd.Function):
+class BilinearGroupFn:
+    """The grouped resize as the glue calls it: apply(spec, *xs, align_corners=False)."""
+
+    @staticmethod
+    def apply(spec, *xs, align_corners=False):
+        return _BilinearGroupFn.apply(spec, bool(align_corners), *xs)
+
+
+class _UpsampleCatGroupFn(torch.autograd.Function):
     """For each group g: cat([y0, up(y1), up(y2), ...], channels) with up = bilinear resize to y0's size
-    (align_corners=False).  The resize kernel writes straight into its channel slice of the concatenated buffer
+    (align_corners as given, kept in ctx for the backward).  The resize kernel writes straight into its channel slice of the concatenated buffer
     (output leading dimension = total channels; y0 goes through the same kernel at scale 1, an exact copy) -- no
     upsampled temporaries, no torch.cat pass over the 720-channel tensor (0.25 ms per step at 1024x1024).  Backward:
     the resize's transposed kernel reads its slice of the incoming gradient in place; y0's gradient IS its slice."""
 
     @staticmethod
-    def forward(ctx, counts, *xs):
+    def forward(ctx, counts, align_corners, *xs):
+        ac = int(bool(align_corners))
         outs, meta, k = [], [], 0
         prep = [_pixels(x) for x in xs]
         with group():
@@ -2033,18 +2051,18 @@ class UpsampleCatGroupFn(torch.autograd.Function):
                 for x, ldx in g:
                     _, Hi, Wi, C = x.shape
                     assert off % 8 == 0, "channel slices must stay 16-byte aligned"
-                    check(lib().ssa_bilinear_fwd(_p(x), _dt(x), B, Hi, Wi, C, ldx, ctypes.c_void_p(y.data_ptr() + 2 * off),
-                                                 _dt(y), Ho, Wo, Ct, _s()), "ssa_bilinear_fwd")
+                    check(lib().ssa_resize_bilinear_fwd(_p(x), _dt(x), B, Hi, Wi, C, ldx, ctypes.c_void_p(y.data_ptr() + 2 * off),
+                                                        _dt(y), Ho, Wo, Ct, ac, _s()), "ssa_resize_bilinear_fwd")
                     meta.append((B, Hi, Wi, C, Ho, Wo, off, Ct))
                     off += C
                 outs.append(y)
                 k += n
-        ctx.counts, ctx.meta = counts, meta
+        ctx.counts, ctx.meta, ctx.align_corners = counts, meta, bool(ac)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dys):
-        dxs, k = [None], 0
+        dxs, k = [None, None], 0
         prep = []
         for dy in dys:
             if dy is None:
@@ -2070,14 +2088,20 @@ class UpsampleCatGroupFn(torch.autograd.Function):
                 jobs.append((ctypes.c_void_p(dy.data_ptr() + 2 * off), _dt(dy), lddy, B, Hi, Wi, C, Ho, Wo, dx))
                 dxs.append(dx)
             k += n
-        _bilinear_bwd_group(jobs)
+        _bilinear_bwd_group(jobs, ctx.align_corners)
         return tuple(dxs)
+
+
+class UpsampleCatGroupFn:
+    @staticmethod
+    def apply(counts, *xs, align_corners=False):
+        return _UpsampleCatGroupFn.apply(counts, bool(align_corners), *xs)
 
 
 class BilinearFn:
     @staticmethod
-    def apply(x, Ho, Wo, out_f32):
-        return BilinearGroupFn.apply(((int(Ho), int(Wo), bool(out_f32)),), x)[0]
+    def apply(x, Ho, Wo, out_f32, align_corners=False):
+        return BilinearGroupFn.apply(((int(Ho), int(Wo), bool(out_f32)),), x, align_corners=align_corners)[0]
 
 
 class MaxPool3x3s2Fn(torch.autograd.Function):
@@ -2219,16 +2243,16 @@ class DwConv3x3Fn(torch.autograd.Function):
         return dx, (None if param or not need_dw else dw), None, None, None
 
 
-def image_to_nhwc(images, out_hw=None, cpad=16):
-    """NCHW fp32 image batch -> NHWC bf16, optionally bilinearly resized."""
+def image_to_nhwc(images, out_hw=None, cpad=16, align_corners=False):
+    """NCHW fp32 image batch -> NHWC bf16, optionally bilinearly resized (ResizeX, under the index rule given)."""
     images = images.detach()
     if images.dtype != torch.float32 or not images.is_contiguous():
         images = images.float().contiguous()
     B, C, H, W = images.shape
     Ho, Wo = out_hw if out_hw is not None else (H, W)
     y = torch.empty((B, Ho, Wo, cpad), dtype=ACT_DTYPE, device=images.device)
-    check(lib().ssa_image_resize_to_nhwc_bf16(_p(images), B, C, H, W, _p(y), Ho, Wo, cpad, _s()),
-          "ssa_image_resize_to_nhwc_bf16")
+    check(lib().ssa_image_resize_to_nhwc(_p(images), B, C, H, W, _p(y), Ho, Wo, cpad, int(bool(align_corners)), _s()),
+          "ssa_image_resize_to_nhwc")
     return y
 
 

@@ -28,6 +28,14 @@ def _lst(v, n):
     return list(v) if _is_list(v) else [v] * n
 
 
+def _align_corners():
+    """cfg.MODEL.ALIGN_CORNERS (the reference's --align_corners), read when a resize is CALLED -- the reference reads it
+    at import (network/mynn.py:15); here a changed flag holds from the next call on.  The HIP backend hands it to the
+    kernels explicitly; a captured step (graphed.py) has the value of its capture baked in."""
+    from .config import cfg
+    return bool(cfg.MODEL.ALIGN_CORNERS)
+
+
 class BackendBase:
     """List-aware front of the operator surface over single-problem primitives
     (`_conv2d`, `_conv_bn_act`, `_batch_norm_act`, `_sum_act`, `_bilinear`)."""
@@ -163,7 +171,7 @@ class HipBackend(BackendBase):
         return self.hb.group()
 
     def image_to_nhwc(self, images, out_hw=None):
-        return self.hb.image_to_nhwc(images, out_hw)
+        return self.hb.image_to_nhwc(images, out_hw, align_corners=_align_corners())
 
     # -- convolution -----------------------------------------------------------------
     def conv2d(self, x, weight, bias, stride, padding, dilation, out_f32=False, want_stats=False):
@@ -340,14 +348,14 @@ class HipBackend(BackendBase):
                 todo.append(i)
                 spec.append((int(s[0]), int(s[1]), bool(out_f32)))
         if todo:
-            ys = self.hb.BilinearGroupFn.apply(tuple(spec), *[xs[i] for i in todo])
+            ys = self.hb.BilinearGroupFn.apply(tuple(spec), *[xs[i] for i in todo], align_corners=_align_corners())
             for i, y in zip(todo, ys):
                 outs[i] = y
         return outs if multi else outs[0]
 
     def upsample_cat(self, groups):
         counts = tuple(len(g) for g in groups)
-        return list(self.hb.UpsampleCatGroupFn.apply(counts, *[t for g in groups for t in g]))
+        return list(self.hb.UpsampleCatGroupFn.apply(counts, *[t for g in groups for t in g], align_corners=_align_corners()))
 
     def max_pool3x3s2(self, x):
         return self.hb.MaxPool3x3s2Fn.apply(x)

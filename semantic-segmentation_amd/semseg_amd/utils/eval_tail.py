@@ -127,16 +127,15 @@ def flip_tensor(x, dim):
 
 
 def resize_tensor(inputs, target_size):
-    """utils/trnval_utils.py:51-55: bilinear, align_corners=False, [B,C,H,W] fp32 through ssa_bilinear_fwd; returns the
-    permuted view of the new NHWC tensor."""
+    """utils/trnval_utils.py:51-55: bilinear, align_corners=cfg.MODEL.ALIGN_CORNERS (read at call time), [B,C,H,W] fp32
+    through ssa_resize_bilinear_fwd; returns the permuted view of the new NHWC tensor."""
     from .. import hip_backend as hb
     from ..config import cfg
-    assert not cfg.MODEL.ALIGN_CORNERS, "only align_corners=False is implemented"
     x = inputs.detach().permute(0, 2, 3, 1)
     if x.dtype != torch.float32:
         x = x.float()
     with torch.no_grad():
-        y = hb.BilinearFn.apply(x, int(target_size[0]), int(target_size[1]), True)
+        y = hb.BilinearFn.apply(x, int(target_size[0]), int(target_size[1]), True, bool(cfg.MODEL.ALIGN_CORNERS))
     return y.permute(0, 3, 1, 2)
 
 
