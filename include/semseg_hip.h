@@ -533,11 +533,73 @@ int ssa_maxpool3x3s2_fwd(const void* x, int ldx, int B, int H, int W, int C, voi
                          unsigned char* idx, int Ho, int Wo, void* stream);
 int ssa_maxpool3x3s2_bwd(const void* dy, const unsigned char* idx, int B, int Ho, int Wo,
                          int C, void* dx, int H, int W, void* stream);
+/* nn.MaxPool2d(3, stride=2, ceil_mode=True) without padding, the stem pool of the SE-ResNeXt trunks
+ * (network/SEresnext.py:271-272): window rows 2 oy .. 2 oy + 2 and columns 2 ox .. 2 ox + 2 clipped to the image (a tap
+ * past the edge never wins), Ho = H / 2, Wo = W / 2, H, W >= 2.  First-maximum / NaN rule and byte index map (tap =
+ * kh * 3 + kw) of the padding-1 pool above.  16-byte aligned x, y, dy, dx (y, dy, dx dense), ldx % 8 == 0, >= C;
+ * anything else returns -1 before the device is touched.                                                        */
+int ssa_maxpool3x3s2c_fwd(const void* x, int ldx, int B, int H, int W, int C, void* y, unsigned char* idx, int Ho,
+                          int Wo, void* stream);
+int ssa_maxpool3x3s2c_bwd(const void* dy, const unsigned char* idx, int B, int Ho, int Wo, int C, void* dx, int H, int W,
+                          void* stream);
 /* out[b,c] = mean_p x[b,p,c];  dx[b,p,c] = dout[b,c] / HW                        */
 int ssa_global_avg_pool_fwd(const void* x, int ldx, int B, long HW, int C, void* out,
                             void* stream);
 int ssa_global_avg_pool_bwd(const void* dout, int B, long HW, int C, void* dx,
                             void* stream);
+
+/* --------------------------------------------------------- grouped 3x3 conv ----
+ * nn.Conv2d(C, C, 3, stride, padding = dilation, dilation, groups = G, bias = False) with 1 < G < C: conv2 of every
+ * SE-ResNeXt bottleneck (network/SEresnext.py:183-185; the stride-8 surgery of network/utils.py:71-81 sets dilation and
+ * padding).  NHWC 16-bit, C % 8 == 0, Cg = C / G in {4, 8, 16, 32} (anything else: -2), pixel strides % 8 and >= C,
+ * 16-byte aligned x, y, dy, dx (ssa_dwconv_desc's rules); w = the parameter's own [C][Cg][3][3] fp32 storage.  The
+ * filter operand of the MFMA is 16-bit: the kernels round the fp32 parameter to the storage type (round to nearest
+ * even), which is part of the contract.  A bad descriptor returns -1 before the device is touched.               */
+typedef struct ssa_gconv_desc {
+  int B, H, W, C, G, ldx;  /* x [B,H,W,C], G groups */
+  int Ho, Wo, ldy;         /* y [B,Ho,Wo,C], Ho = (H-1)/stride + 1 */
+  int stride, dil;         /* stride 1 with dil >= 1, or stride 2 with dil 1; padding = dil */
+} ssa_gconv_desc;
+/* y = round16(sum over the group's Cg input channels and the 9 taps of round16(w) x).  stats (training; replaces the
+ * ssa_bn_stats pass of bn2): sum y and sum y^2 of the values AS STORED are added into [ssa_bn_stat_replicas()][2][C]
+ * fp64 (caller clears) -- ssa_dwconv3x3's contract.                                                              */
+int ssa_gconv3x3(const ssa_gconv_desc* d, const void* x, const float* w, void* y, double* stats, void* stream);
+/* Backward of the same conv (cuDNN's backward-data and backward-filter behind the grouped nn.Conv2d): dx (nullable)
+ * [B,H,W,C] 16-bit, every pixel written; dw (nullable) [C][Cg][3][3] fp32, added to when accumulate != 0, summed in a
+ * fixed order.  ws: ssa_gconv3x3_bwd_plan's bytes (the workgroups' fp32 partial tiles of dw; needed with dw).  x is
+ * needed with dw, w with dx.  Asking for neither returns -1.                                                    */
+int ssa_gconv3x3_bwd_plan(const ssa_gconv_desc* d, size_t* ws_bytes);
+int ssa_gconv3x3_bwd(const ssa_gconv_desc* d, const void* x, const void* dy, int lddy, const float* w, void* dx,
+                     int lddx, float* dw, int accumulate, void* ws, void* stream);
+
+/* ------------------------------------------------- squeeze-and-excitation gate ----
+ * z = relu(se_module(y) + residual), se_module(y) = y * sigmoid(fc2(relu(fc1(avg_pool(y))))): SEModule.forward and the
+ * tail of Bottleneck.forward (network/SEresnext.py:84-91, 115-116).  y, r, z, dz, dy, dr: NHWC 16-bit [B,HW,C] with
+ * pixel strides % 8 == 0 and >= C, 16-byte aligned, C % 8 == 0.  The gate reads the fp32 parameters in their own
+ * storage -- w1 [Cr][C], b1 [Cr], w2 [C][Cr], b2 [C] (fc1 / fc2 are 1x1 convs) -- and all of its arithmetic is fp32;
+ * mean [B][C], h [B][Cr], s [B][C], ds, g [B][C] are fp32.  Every sum has a fixed order (no atomics).  ws: ssa_se_plan's
+ * bytes, one size for all entry points of a (B, HW, C, Cr).  A bad argument returns -1, Cr > min(C, 1024) -2, before
+ * the device is touched.                                                                                          */
+int ssa_se_plan(int B, long HW, int C, int Cr, size_t* ws_bytes);
+/* squeeze + gate (replaces avg_pool, fc1, relu, fc2, sigmoid: SEresnext.py:86-90): mean = sum_p y / HW, summed by as
+ * many workgroups as fill the chip; h = relu(W1 mean + b1); s = 1 / (1 + exp(-(W2 h + b2))).                      */
+int ssa_se_squeeze_gate(const void* y, int ldy, int B, long HW, int C, int Cr, const float* w1, const float* b1,
+                        const float* w2, const float* b2, float* mean, float* h, float* s, void* ws, void* stream);
+/* apply (replaces `module_input * x`, `+ residual` and `self.relu`: SEresnext.py:91, 115-116):
+ * z = round16(act(fma(s[b,c], y, r))); r nullable (no residual), the ReLU only if relu != 0.                     */
+int ssa_se_apply(const void* y, int ldy, const void* r, int ldr, const float* s, void* z, int ldz, int B, long HW, int C,
+                 int relu, void* stream);
+/* backward, pass 1 over dz: ds[b,c] = sum_p m dz y, m = (z > 0) with relu != 0 (z then required), else 1.         */
+int ssa_se_bwd_reduce(const void* dz, int lddz, const void* z, int ldz, const void* y, int ldy, int B, long HW, int C,
+                      int relu, float* ds, void* ws, void* stream);
+/* gate backward: a2 = ds s (1 - s); db2 = sum_b a2; dw2 = sum_b a2 h^T; a1 = (W2^T a2) (h > 0); db1 = sum_b a1;
+ * dw1 = sum_b a1 mean^T; g = (W1^T a1) / HW -- the gradients are written, or added to when accumulate != 0.       */
+int ssa_se_gate_bwd(const float* ds, const float* s, const float* h, const float* mean, const float* w1, const float* w2,
+                    int B, long HW, int C, int Cr, float* g, float* dw1, float* db1, float* dw2, float* db2, int accumulate,
+                    void* ws, void* stream);
+/* backward, pass 2 over dz: dy = round16(fma(s[b,c], m dz, g[b,c])), dr = round16(m dz) (dr nullable).            */
+int ssa_se_apply_bwd(const void* dz, int lddz, const void* z, int ldz, const float* s, const float* g, int B, long HW, int C,
+                     int relu, void* dy, int lddy, void* dr, int lddr, void* stream);
 
 /* ------------------------------------------------------- depthwise 3x3 conv ----
  * nn.Conv2d(C, C, 3, stride, padding = dilation, dilation, groups = C, bias = False), the first half of every

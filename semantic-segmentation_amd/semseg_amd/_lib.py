@@ -78,6 +78,11 @@ class DwConvDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("B", "H", "W", "C", "ldx", "Ho", "Wo", "ldy", "stride", "dil")]
 
 
+class GConvDesc(ctypes.Structure):
+    """Mirror of ssa_gconv_desc."""
+    _fields_ = [(n, c_int) for n in ("B", "H", "W", "C", "G", "ldx", "Ho", "Wo", "ldy", "stride", "dil")]
+
+
 class JitterProgram(ctypes.Structure):
     """Mirror of ssa_jitter_program (36 bytes)."""
     _fields_ = [("n_ops", c_int), ("op", c_int * 4), ("factor", c_float * 3), ("hue_byte", c_int)]
@@ -183,6 +188,17 @@ _SIGS = {
     "ssa_resize_bilinear_bwd_y": ([_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P], c_int),
     "ssa_maxpool3x3s2_fwd": ([_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P], c_int),
     "ssa_maxpool3x3s2_bwd": ([_P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P], c_int),
+    "ssa_maxpool3x3s2c_fwd": ([_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P], c_int),
+    "ssa_maxpool3x3s2c_bwd": ([_P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P], c_int),
+    "ssa_gconv3x3": ([POINTER(GConvDesc), _P, _P, _P, _P, _P], c_int),
+    "ssa_gconv3x3_bwd_plan": ([POINTER(GConvDesc), POINTER(c_size_t)], c_int),
+    "ssa_gconv3x3_bwd": ([POINTER(GConvDesc), _P, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P], c_int),
+    "ssa_se_plan": ([c_int, c_long, c_int, c_int, POINTER(c_size_t)], c_int),
+    "ssa_se_squeeze_gate": ([_P, c_int, c_int, c_long, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
+    "ssa_se_apply": ([_P, c_int, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, _P], c_int),
+    "ssa_se_bwd_reduce": ([_P, c_int, _P, c_int, _P, c_int, c_int, c_long, c_int, c_int, _P, _P, _P], c_int),
+    "ssa_se_gate_bwd": ([_P, _P, _P, _P, _P, _P, c_int, c_long, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P], c_int),
+    "ssa_se_apply_bwd": ([_P, c_int, _P, c_int, _P, _P, c_int, c_long, c_int, c_int, _P, c_int, _P, c_int, _P], c_int),
     "ssa_dwconv3x3": ([POINTER(DwConvDesc), _P, _P, _P, _P, _P, c_int, _P], c_int),
     "ssa_dwconv3x3_bwd_plan": ([POINTER(DwConvDesc), POINTER(c_size_t)], c_int),
     "ssa_dwconv3x3_bwd": ([POINTER(DwConvDesc), _P, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P], c_int),

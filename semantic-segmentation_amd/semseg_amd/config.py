@@ -32,6 +32,7 @@ def _defaults():
         HRNET_CHECKPOINT="",         # config.py:147 (empty: random init, no file needed)
         WRN38_CHECKPOINT="",         # config.py:145 (empty: random init; else network/wider_resnet.py:405-409)
         X71_CHECKPOINT="",           # config.py:145-146 (empty: random init; else network/xception.py:270-279)
+        SRNX_CHECKPOINT="",          # (empty: random init; else a LOCAL file, network/seresnext.py -- the reference downloads)
         OCR=AttrDict(MID_CHANNELS=512, KEY_CHANNELS=256),   # config.py:157-158
         # cfg.MODEL.OCR_EXTRA, config.py:161-190 (HRNetV2-W48)
         OCR_EXTRA=AttrDict(
@@ -73,7 +74,7 @@ def sync_from_reference(ref_cfg):
     """Copy the fields the hot path reads from the reference's global cfg."""
     m = ref_cfg.MODEL
     for k in ("ALIGN_CORNERS", "MSCALE", "MSCALE_LO_SCALE", "N_SCALES", "SEGATTN_BOT_CH", "ASPP_BOT_CH", "MSCALE_INNER_3x3",
-              "HRNET_CHECKPOINT", "WRN38_CHECKPOINT", "X71_CHECKPOINT"):
+              "HRNET_CHECKPOINT", "WRN38_CHECKPOINT", "X71_CHECKPOINT", "SRNX_CHECKPOINT"):
         if hasattr(m, k):
             cfg.MODEL[k] = getattr(m, k)
     cfg.MODEL.OCR.MID_CHANNELS = m.OCR.MID_CHANNELS

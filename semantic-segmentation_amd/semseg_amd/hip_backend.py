@@ -29,7 +29,7 @@ import weakref
 
 import torch
 
-from ._lib import lib, check, ConvDesc, DwConvDesc, PackJob, BnUpdateJob, BnEvalJob, ProfileRec
+from ._lib import lib, check, ConvDesc, DwConvDesc, GConvDesc, PackJob, BnUpdateJob, BnEvalJob, ProfileRec
 
 from ._lib import ACT as _ACT_NAME     # storage format of the activations = the library build (SSA_ACT_DTYPE)
 ACT_DTYPE = torch.float16 if _ACT_NAME == "fp16" else torch.bfloat16
@@ -2241,6 +2241,182 @@ class DwConv3x3Fn(torch.autograd.Function):
         if need_dw and not param and dw.dtype != weight.dtype:
             dw = dw.to(weight.dtype)
         return dx, (None if param or not need_dw else dw), None, None, None
+
+
+# --------------------------------------------------------------------------
+# SE-ResNeXt trunk (network/SEresnext.py): the ceil-mode stem pool and the squeeze-and-excitation gate
+# --------------------------------------------------------------------------
+def _act_operand(t, C):
+    """(t as dense pixels, ld) for an entry point that wants pixel strides % 8 and 16-byte alignment."""
+    assert t.dim() == 4 and t.dtype == ACT_DTYPE and t.shape[3] == C, (tuple(t.shape), t.dtype, C)
+    t, ld = _pixels(t)
+    if t.data_ptr() % 16 or ld % 8:
+        t, ld = t.contiguous(), C
+    return t, ld
+
+
+class MaxPool3x3s2CeilFn(torch.autograd.Function):
+    """nn.MaxPool2d(3, stride=2, ceil_mode=True), no padding, on NHWC 16-bit (SE-ResNeXt stem): [B,H,W,C] ->
+    [B,H//2,W//2,C]."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, H, W, C = x.shape
+        x, ldx = _act_operand(x, C)
+        Ho, Wo = H // 2, W // 2
+        y = torch.empty((B, Ho, Wo, C), dtype=ACT_DTYPE, device=x.device)
+        idx = torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=x.device)
+        check(lib().ssa_maxpool3x3s2c_fwd(_p(x), ldx, B, H, W, C, _p(y), _p(idx), Ho, Wo, _s()), "ssa_maxpool3x3s2c_fwd")
+        ctx.save_for_backward(idx)
+        ctx.meta = (B, H, W, C, Ho, Wo)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        B, H, W, C, Ho, Wo = ctx.meta
+        dy = (dy if dy.dtype == ACT_DTYPE else dy.to(ACT_DTYPE)).contiguous()
+        dx = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dy.device)
+        check(lib().ssa_maxpool3x3s2c_bwd(_p(dy), _p(idx), B, Ho, Wo, C, _p(dx), H, W, _s()), "ssa_maxpool3x3s2c_bwd")
+        return dx
+
+
+def _se_ws(B, HW, C, Cr, device):
+    n = ctypes.c_size_t(0)
+    check(lib().ssa_se_plan(B, HW, C, Cr, ctypes.byref(n)), "ssa_se_plan")
+    # written before it is read by every entry point; the caching allocator hands the block on (a captured step replays
+    # the same addresses), as the depthwise backward's workspace
+    return torch.empty((n.value // 4,), dtype=torch.float32, device=device)
+
+
+def _f32c(t):
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+class SeGateFn(torch.autograd.Function):
+    """z = act(sigmoid(fc2(relu(fc1(mean_hw(y))))) * y + residual) on NHWC 16-bit (network/SEresnext.py:84-91, 115-116);
+    fc1 / fc2: the 1x1 convs' own fp32 parameters ([Cr,C,1,1], [Cr], [C,Cr,1,1], [C]).  Forward: ssa_se_squeeze_gate +
+    ssa_se_apply.  Backward: ssa_se_bwd_reduce, ssa_se_gate_bwd, ssa_se_apply_bwd on the current stream; a parameter's
+    gradient is added into its gradient-arena slice.  Nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, y, residual, w1, b1, w2, b2, relu):
+        B, H, W, C = y.shape
+        Cr = w1.shape[0]
+        assert tuple(w1.shape) == (Cr, C, 1, 1) and tuple(w2.shape) == (C, Cr, 1, 1) and b1.numel() == Cr and b2.numel() == C
+        y, ldy = _act_operand(y, C)
+        r, ldr = (None, 0) if residual is None else _act_operand(residual, C)
+        dev = y.device
+        mean = torch.empty((B, C), dtype=torch.float32, device=dev)
+        h = torch.empty((B, Cr), dtype=torch.float32, device=dev)
+        s = torch.empty((B, C), dtype=torch.float32, device=dev)
+        z = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev)
+        ws = _se_ws(B, H * W, C, Cr, dev)
+        _note(2.0 * B * H * W * C + 4.0 * B * C * Cr, 2.0 * B * H * W * C * (3 + int(r is not None)))
+        check(lib().ssa_se_squeeze_gate(_p(y), ldy, B, H * W, C, Cr, _p(_f32c(w1)), _p(_f32c(b1)), _p(_f32c(w2)), _p(_f32c(b2)),
+                                        _p(mean), _p(h), _p(s), _p(ws), _s()), "ssa_se_squeeze_gate")
+        check(lib().ssa_se_apply(_p(y), ldy, _p(r), ldr, _p(s), _p(z), C, B, H * W, C, int(bool(relu)), _s()), "ssa_se_apply")
+        ctx.save_for_backward(y, z, s, h, mean, w1, b1, w2, b2)
+        ctx.meta = (ldy, bool(relu), residual is not None)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        y, z, s, h, mean, w1, b1, w2, b2 = ctx.saved_tensors
+        ldy, relu, has_res = ctx.meta
+        B, H, W, C = y.shape
+        Cr, HW, dev = w1.shape[0], H * W, y.device
+        dzb, lddz = _dz_bf16(dz, C)
+        ws = _se_ws(B, HW, C, Cr, dev)
+        ds = torch.empty((B, C), dtype=torch.float32, device=dev)
+        g = torch.empty((B, C), dtype=torch.float32, device=dev)
+        _note(4.0 * B * HW * C, 2.0 * B * HW * C * (6 + int(has_res)))
+        check(lib().ssa_se_bwd_reduce(_p(dzb), lddz, _p(z), C, _p(y), ldy, B, HW, C, int(relu), _p(ds), _p(ws), _s()),
+              "ssa_se_bwd_reduce")
+        params = (w1, b1, w2, b2)
+        arena = all(_is_param(p) for p in params)           # the four go together: one accumulate flag
+        grads = [_GRADS.slot(p) if arena else torch.empty(p.shape, dtype=torch.float32, device=dev) for p in params]
+        check(lib().ssa_se_gate_bwd(_p(ds), _p(s), _p(h), _p(mean), _p(_f32c(w1)), _p(_f32c(w2)), B, HW, C, Cr, _p(g),
+                                    _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(grads[3]), int(arena), _p(ws), _s()),
+              "ssa_se_gate_bwd")
+        need_dr = has_res and ctx.needs_input_grad[1]
+        dy = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev)
+        dr = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=dev) if need_dr else None
+        check(lib().ssa_se_apply_bwd(_p(dzb), lddz, _p(z), C, _p(s), _p(g), B, HW, C, int(relu), _p(dy), C, _p(dr), C, _s()),
+              "ssa_se_apply_bwd")
+        pg = [None] * 4 if arena else [gr.to(p.dtype) if ctx.needs_input_grad[2 + i] else None
+                                       for i, (gr, p) in enumerate(zip(grads, params))]
+        return (dy if ctx.needs_input_grad[0] else None), dr, pg[0], pg[1], pg[2], pg[3], None
+
+
+# --------------------------------------------------------------------------
+# grouped 3x3 conv, 1 < groups < C (network/SEresnext.py:183-185: conv2 of the SE-ResNeXt bottleneck)
+# --------------------------------------------------------------------------
+GCONV_GROUP_WIDTHS = (4, 8, 16, 32)
+
+
+def gconv_supported(x, weight, stride, dil, groups):
+    """The forms csrc/gconv.hip is built for (ssa_gconv3x3 returns -2 for the others)."""
+    C = weight.shape[0]
+    return x.dtype == ACT_DTYPE and C % 8 == 0 and C % groups == 0 and C // groups in GCONV_GROUP_WIDTHS and \
+        tuple(weight.shape[1:]) == (C // groups, 3, 3) and ((stride == 1 and dil >= 1) or (stride == 2 and dil == 1))
+
+
+def _gc_desc(x, ldx, stride, dil, groups, ldy):
+    B, H, W, C = x.shape
+    return GConvDesc(B, H, W, C, groups, ldx, (H - 1) // stride + 1, (W - 1) // stride + 1, ldy, stride, dil)
+
+
+class GConv3x3Fn(torch.autograd.Function):
+    """nn.Conv2d(C, C, 3, stride, padding = dil, dil, groups, bias = False) on NHWC: x 16-bit, weight [C,C/groups,3,3]
+    fp32 (rounded to the storage type inside the kernels).  want_stats: the kernel also takes the batch statistics of its
+    stored output and leaves them for the BatchNorm that consumes it (_PENDING_STATS, as DwConv3x3Fn).  Backward: the data
+    gradient and the weight gradient (ssa_gconv3x3_bwd) on the current stream; a parameter's gradient is added into its
+    gradient-arena slice."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, dil, groups, want_stats):
+        C = x.shape[3]
+        x, ldx = _act_operand(x, C)
+        w = _f32c(weight)
+        d = _gc_desc(x, ldx, stride, dil, groups, C)
+        stats = _ARENA.take(stat_replicas() * 2 * C, x.device) if want_stats else None
+        y = torch.empty((x.shape[0], d.Ho, d.Wo, C), dtype=ACT_DTYPE, device=x.device)
+        _note(18.0 * (C // groups) * y.numel(), 2.0 * (x.numel() + y.numel()))
+        check(lib().ssa_gconv3x3(ctypes.byref(d), _p(x), _p(w), _p(y), _p(stats), _s()), "ssa_gconv3x3")
+        if stats is not None:
+            _PENDING_STATS[y.data_ptr()] = (stats, stat_replicas())      # picked up (SyncBN: exchanged) by _bn_train_fwd
+        ctx.save_for_backward(x, weight)
+        ctx.meta = (ldx, stride, dil, groups)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        ldx, stride, dil, groups = ctx.meta
+        B, H, W, C = x.shape
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if dy is None or not (need_dx or need_dw):
+            return None, None, None, None, None, None
+        dyb, lddy = _dz_bf16(dy, C)
+        d = _gc_desc(x, ldx, stride, dil, groups, C)
+        dx = torch.empty((B, H, W, C), dtype=ACT_DTYPE, device=x.device) if need_dx else None
+        dw = ws = None
+        param = need_dw and _is_param(weight)
+        if need_dw:
+            dw = _GRADS.slot(weight) if param else torch.empty(weight.shape, dtype=torch.float32, device=x.device)
+            n = ctypes.c_size_t(0)
+            check(lib().ssa_gconv3x3_bwd_plan(ctypes.byref(d), ctypes.byref(n)), "ssa_gconv3x3_bwd_plan")
+            # the workgroups' partial tiles: written before they are read, freed with this node (DwConv3x3Fn's scheme)
+            ws = torch.empty((n.value // 4,), dtype=torch.float32, device=x.device)
+        _note(18.0 * (C // groups) * B * d.Ho * d.Wo * C * (int(need_dx) + int(need_dw)),
+              2.0 * C * (B * d.Ho * d.Wo + B * H * W) * (int(need_dx) + int(need_dw)))
+        check(lib().ssa_gconv3x3_bwd(ctypes.byref(d), _p(x), _p(dyb), lddy, _p(_f32c(weight)), _p(dx), C, _p(dw), int(param),
+                                     _p(ws), _s()), "ssa_gconv3x3_bwd")
+        if need_dw and not param and dw.dtype != weight.dtype:
+            dw = dw.to(weight.dtype)
+        return dx, (None if param or not need_dw else dw), None, None, None, None
 
 
 def image_to_nhwc(images, out_hw=None, cpad=16, align_corners=False):

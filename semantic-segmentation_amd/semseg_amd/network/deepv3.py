@@ -3,7 +3,8 @@ the `--arch deepv3.DeepV3PlusR50` of BASELINE.json configs[0].  Same factory
 name, call contract and state_dict (363 keys); NHWC bf16 on the HIP kernels.
 `DeepV3PlusW38` / `DeepV3PlusW38I` (network/deepv3.py:108-114): the same head on
 the WiderResNet-38 trunk of scripts/train_cityscapes_deepv3.yml; `DeepV3PlusX71` (network/deepv3.py:117-118): on the
-Xception-71 trunk (network/xception.py)."""
+Xception-71 trunk (network/xception.py); `DeepV3PlusSRNX50` / `DeepV3PlusSRNX101` (network/deepv3.py:96-105): on the
+SE-ResNeXt trunks (network/seresnext.py)."""
 import torch
 from torch import nn
 
@@ -108,3 +109,11 @@ def DeepV3PlusW38I(num_classes, criterion):
 
 def DeepV3PlusX71(num_classes, criterion):
     return DeepV3Plus(num_classes, trunk="xception71", criterion=criterion)
+
+
+def DeepV3PlusSRNX50(num_classes, criterion):
+    return DeepV3Plus(num_classes, trunk="seresnext-50", criterion=criterion)
+
+
+def DeepV3PlusSRNX101(num_classes, criterion):
+    return DeepV3Plus(num_classes, trunk="seresnext-101", criterion=criterion)

@@ -79,6 +79,13 @@ class ResNetTrunk(nn.Module):
 
 
 def get_resnet(trunk_name, output_stride=8):
+    """network/utils.py:48-99: the trunk with layer0 .. layer4 and the stride-8 surgery applied."""
+    if trunk_name == "seresnext-50":
+        from .seresnext import SEResNeXtTrunk
+        return SEResNeXtTrunk((3, 4, 6, 3), output_stride)
+    if trunk_name == "seresnext-101":
+        from .seresnext import SEResNeXtTrunk
+        return SEResNeXtTrunk((3, 4, 23, 3), output_stride)
     if trunk_name != "resnet-50":
         raise ValueError("Not a valid network arch")
     return ResNetTrunk((3, 4, 6, 3), output_stride)

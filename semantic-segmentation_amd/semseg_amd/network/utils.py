@@ -12,7 +12,9 @@ from ..nn import Conv2d, Norm2d, BNReLU, conv_bn  # noqa: F401  (BNReLU re-expor
 def get_trunk(trunk_name, output_stride=8):
     """network/utils.py:102-141 -- the trunks of BASELINE.json's configs: HRNetV2-W48
     (hot path) and ResNet-50 (DeepLabV3+ plumbing config), WiderResNet-38 (scripts/train_cityscapes_deepv3.yml) and
-    Xception-71 (deepv3.DeepV3PlusX71)."""
+    Xception-71 (deepv3.DeepV3PlusX71), SE-ResNeXt-50 / -101 (deepv3.DeepV3PlusSRNX50 / SRNX101).  The reference returns
+    s2_ch = 48 for the SE-ResNeXt trunks although their layer1 delivers 256 channels, and its DeepV3PlusSRNX50 cannot
+    run a forward (bot_fine raises); here s2_ch is 256."""
     assert output_stride == 8, "Only stride8 supported right now"
     if trunk_name == "hrnetv2":
         from . import hrnetv2
@@ -27,7 +29,11 @@ def get_trunk(trunk_name, output_stride=8):
     if trunk_name == "xception71":
         from .xception import xception71
         return xception71(output_stride=output_stride, pretrained=True), 64, 128, 2048
-    raise ValueError("unsupported trunk {} (supported: hrnetv2, resnet-50, wrn38, xception71)".format(trunk_name))
+    if trunk_name in ("seresnext-50", "seresnext-101"):
+        from .resnet import get_resnet
+        return get_resnet(trunk_name, output_stride=output_stride), 256, -1, 2048
+    raise ValueError("unsupported trunk {} (supported: hrnetv2, resnet-50, wrn38, xception71, seresnext-50, "
+                     "seresnext-101)".format(trunk_name))
 
 
 class ConvBnRelu(nn.Module):

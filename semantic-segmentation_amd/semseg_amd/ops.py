@@ -105,6 +105,54 @@ class BackendBase:
         assert not _is_list(x), "separable_conv_bn_act takes one problem"
         return self.conv_bn_act(sep.pointwise, bn, self.depthwise_conv_bn(sep, x), residual, relu)
 
+    def grouped_conv(self, x, weight, stride, dilation, groups, want_stats=False):
+        """nn.Conv2d(C, C, 3, stride, padding = dilation, dilation, groups, bias = False) with 1 < groups < C
+        (network/SEresnext.py:183-185 after the surgery of network/utils.py:71-81).  One problem.  The form of
+        depthwise_conv: the [C,C/groups,3,3] weight copied onto the block diagonal of a dense [C,C,3,3] filter
+        (differentiably; the other products are exact zeros), through the backend's own dense conv."""
+        assert not _is_list(x), "grouped_conv takes one problem"
+        C, Cg = weight.shape[0], weight.shape[1]
+        assert C == Cg * groups, (tuple(weight.shape), groups)
+        return self._conv2d(x, self._block_diagonal(weight, groups), None, stride, dilation, dilation)
+
+    @staticmethod
+    def _block_diagonal(weight, groups, padded=False):
+        """[C, C / groups, kh, kw] -> the dense [C, C, kh, kw] filter with the groups on the block diagonal.  One strided
+        copy into the diagonal view of a zero tensor (differentiable: the weight's gradient is that view of the dense
+        filter's), no index tensors.  padded: the rows of the result have a spare element, so the result is not
+        contiguous (HipBackend.grouped_conv says why)."""
+        C, Cg, kh, kw = weight.shape
+        assert C == Cg * groups, (tuple(weight.shape), groups)
+        dense = weight.new_zeros((C, C, kh, kw + int(bool(padded))))[..., :kw]
+        diag = torch.diagonal(dense.view(groups, Cg, groups, Cg, kh, kw), 0, 0, 2)        # [Cg, Cg, kh, kw, groups]
+        diag.copy_(weight.view(groups, Cg, Cg, kh, kw).permute(1, 2, 3, 4, 0))
+        return dense
+
+    def grouped_conv_bn_act(self, conv, bn, x, relu=False):
+        """Grouped 3x3 `conv` -> bn (-> ReLU): conv2 / bn2 of an SE-ResNeXt bottleneck (network/SEresnext.py:105-107).
+        One problem."""
+        assert conv.kernel_size == (3, 3) and conv.bias is None and conv.padding[0] == conv.dilation[0] and \
+            conv.in_channels == conv.out_channels and conv.padding_mode == "zeros"
+        y = self.grouped_conv(x, conv.weight, conv.stride[0], conv.dilation[0], conv.groups, want_stats=bn.training)
+        return self.batch_norm_act(y, bn, None, relu, None)
+
+    def max_pool3x3s2_ceil(self, x):
+        """nn.MaxPool2d(3, stride=2, ceil_mode=True), no padding (network/SEresnext.py:271-272): [B,H,W,C] ->
+        [B,H//2,W//2,C] for H, W >= 2; a window that overhangs the edge takes the taps it has."""
+        y = torch.nn.functional.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 0, ceil_mode=True)
+        return y.permute(0, 2, 3, 1)
+
+    def se_gate_add_act(self, se, y, residual=None, relu=True):
+        """Squeeze-and-excitation gate and the block tail behind it (network/SEresnext.py:84-91, 115-116):
+        s = sigmoid(fc2(relu(fc1(mean_hw(y))))) per (image, channel), z = act(s * y + residual).  One problem."""
+        m = self.global_avg_pool(y)
+        h = self.relu(self._conv2d(m, se.fc1.weight, se.fc1.bias, 1, 0, 1))
+        s = self.sigmoid(self._conv2d(h, se.fc2.weight, se.fc2.bias, 1, 0, 1))
+        z = s.to(y.dtype) * y
+        if residual is not None:
+            z = z + residual
+        return torch.relu(z) if relu else z
+
     def basic_block(self, blocks, xs):
         """conv3x3-BN-ReLU-conv3x3-BN-(+x)-ReLU (network/hrnetv2.py:37-66, no downsample branch)
         of blocks[i] on xs[i]."""
@@ -362,6 +410,43 @@ class HipBackend(BackendBase):
 
     def global_avg_pool(self, x):
         return self.hb.GlobalAvgPoolFn.apply(x)
+
+    def max_pool3x3s2_ceil(self, x):
+        return self.hb.MaxPool3x3s2CeilFn.apply(x)
+
+    # (C, stride, dilation) -> True: the grouped kernels of csrc/gconv.hip; False: the block-diagonal dense filter
+    # through the implicit-GEMM conv.  The ship rule: a shape takes the grouped kernels only where tools/gconvbench.py
+    # measured them faster in the sum of forward and both gradients (profiles/gconv_bench.json); shapes never measured
+    # take the grouped kernels (32x fewer multiply-adds at 32 groups).  Layer1's 200 x 200 x 128 (Cg = 4) loses on the
+    # weight gradient's gather: the captured 800 x 800 step is 16.9 ms with it on the dense route, 17.4 ms without.
+    GCONV_ROUTE = {(128, 1, 1): False}
+
+    def grouped_conv(self, x, weight, stride, dilation, groups, want_stats=False):
+        assert not _is_list(x), "grouped_conv takes one problem"
+        if not self.hb.gconv_supported(x, weight, int(stride), int(dilation), int(groups)) or \
+                not self.GCONV_ROUTE.get((weight.shape[0], int(stride), int(dilation)), True):
+            # The dense filter is a temporary.  A contiguous fp32 filter would enter the packed-filter cache under its
+            # storage address and reset the device job tables of the batched re-pack every step; the next step's
+            # begin_step would rebuild them with host-to-device copies, which a stream capture refuses.  A filter that is
+            # not contiguous is packed from a copy and never registered (hip_backend._packed_filter).
+            return HipBackend.conv2d(self, x, self._block_diagonal(weight, groups, padded=True), None, stride, dilation,
+                                     dilation, want_stats=want_stats)
+        return self.hb.GConv3x3Fn.apply(x, weight, int(stride), int(dilation), int(groups), bool(want_stats))
+
+    def grouped_conv_bn_act(self, conv, bn, x, relu=False):
+        """Training: bn's statistics ride on the grouped conv kernel (or on the dense conv's epilogue), no ssa_bn_stats
+        pass; evaluation: the separate apply launch."""
+        assert conv.kernel_size == (3, 3) and conv.bias is None and conv.padding[0] == conv.dilation[0] and \
+            conv.in_channels == conv.out_channels and conv.padding_mode == "zeros"
+        y = HipBackend.grouped_conv(self, x, conv.weight, conv.stride[0], conv.dilation[0], conv.groups,
+                                    want_stats=bn.training)
+        return HipBackend.batch_norm_act(self, y, bn, None, relu)
+
+    def se_gate_add_act(self, se, y, residual=None, relu=True):
+        assert not _is_list(y), "se_gate_add_act takes one problem"
+        if y.dtype != self.act_dtype or y.shape[3] % 8:
+            raise NotImplementedError("the SE gate kernels take NHWC %s with C %% 8 == 0" % self.act_dtype)
+        return self.hb.SeGateFn.apply(y, residual, se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias, bool(relu))
 
     def cat(self, tensors):
         if len(tensors) == 2 and self.hb.adjacent_slices(tensors[0], tensors[1]):
