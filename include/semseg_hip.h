@@ -968,6 +968,36 @@ int ssa_class_centroids_u8(const unsigned char* labels, int N, int H, int W, int
 int ssa_pad_u8(const unsigned char* src, int H, int W, int channels, int left, int top, int right, int bottom,
                const unsigned char* fill, unsigned char* dst, void* stream);
 
+/* The label half of the auto-labelled coarse data path (csrc/autolabel.hip), over N items of one size: what
+ * BaseLoader.read_images and the thresholding of __getitem__ (datasets/base_loader.py:152-229; compare_current = 1) and
+ * the id2trainid loop of class_centroids_image (datasets/uniform.py:104-121; compare_current = 0) make of an
+ * auto-label map `labels`, the gtCoarse labelIds map `coarse` and the `_prob.png` map `prob`, uint8 [N][H][ld_*] on the
+ * device, ld_* >= W.  With o = labels inside the window [win_x0, win_x1) x [win_y0, win_y1) and 0 outside it (the drop
+ * mask, base_loader.py:59-60, 173-174; an EMPTY window, x1 <= x0 or y1 <= y0, means no drop mask), g = coarse and, per
+ * image, mask = cmp = o:
+ *     for (k, v, boost) in steps, in order:
+ *         hit = (cmp == k)                         compare_current = 1: cmp IS mask, as rewritten so far
+ *                                                  compare_current = 0: cmp stays the untouched o
+ *         if boost and hit is non-empty in THIS image:  hit |= (g == k)
+ *         mask[hit] = v
+ *     out = prob < prob_cut ? ignore_label : mask          (prob_cut = 0: no threshold; the host forms
+ *                                                           prob_cut = #{b in 0..255 : b / 255.0 < CUSTOM_COARSE_PROB})
+ * steps: n_steps x (key, value, boost) HOST bytes, 0 <= n_steps <= 256 (0: the identity); they travel as kernel
+ * arguments, so a captured call has them baked in.  coarse may be NULL when no step is boosted (g reads as 0), prob
+ * when prob_cut == 0.  Workspaces on the device, both written before they are read: pairs, uint32 [N][2048], the
+ * (o, g) pairs that occur in each image as a bit set; table, uint8 [N][65536], table[o][g] = the value of the pair after
+ * the steps, written for the pairs that occur and for no other (the apply pass reads only those).  out: uint8 [N][H][ld_out], ld_out >= W; the bytes
+ * between W and ld_out are not written.  The outputs must not overlap the inputs.  FOUR launches whatever the arguments
+ * (clear, pair presence, resolve with one workgroup per image, apply), none when N * H * W == 0; no host synchronisation,
+ * no allocation; capturable, and a replay follows the data.  Returns -1 before touching the device on a null labels /
+ * pairs / table / out, a misaligned pairs, ld < W, n_steps outside 0..256, a boosted step without coarse, prob_cut
+ * outside 0..256 or without prob, ignore_label outside 0..255, compare_current outside 0..1 and a non-empty window that
+ * leaves the image.                                                                                                */
+int ssa_autolabel_u8(const unsigned char* labels, const unsigned char* coarse, const unsigned char* prob, int N, int H,
+                     int W, int ld_labels, int ld_coarse, int ld_prob, const unsigned char* steps, int n_steps,
+                     int compare_current, int win_x0, int win_y0, int win_x1, int win_y1, int prob_cut, int ignore_label,
+                     unsigned int* pairs, unsigned char* table, unsigned char* out, int ld_out, void* stream);
+
 /* Evaluation tail on the device (utils/trnval_utils.py:173-196 + utils/misc.py:50-67
  * fast_hist): pred[p] = first argmax_c logits[p,c] (uint8, optional) and
  * hist[gt*C + pred] += 1 for 0 <= gt < C (int64 [C*C], ACCUMULATED: clear it once per

@@ -260,6 +260,8 @@ _SIGS = {
                         _P, _P, _P], c_int),
     "ssa_class_centroids_u8": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
     "ssa_pad_u8": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_char_p, _P, _P], c_int),
+    "ssa_autolabel_u8": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_char_p, c_int, c_int, c_int, c_int,
+                          c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P], c_int),
     "ssa_confusion_matrix": ([_P, c_int, _P, c_long, c_int, _P, _P, _P], c_int),
     "ssa_eval_tail": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P,
                        _P, _P], c_int),

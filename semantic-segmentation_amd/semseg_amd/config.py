@@ -53,6 +53,12 @@ def _defaults():
         TRANSLATE_AUG_FIX=False,     # config.py:112 (--translate_aug_fix, config.py:266-267)
         MEAN=[0.485, 0.456, 0.406],  # config.py:96-97: what ImageDumper de-normalises with (utils/dumper.py)
         STD=[0.229, 0.224, 0.225],
+        # the auto-labelled coarse data path (datasets/autolabel.py; base_loader.py:152-229, uniform.py:104-121)
+        CITYSCAPES_DIR="/home/dcg-adlr-atao-data.cosmos277/assets/data/Cityscapes",                     # config.py:78-79
+        CITYSCAPES_CUSTOMCOARSE="/home/dcg-adlr-atao-data.cosmos277/assets/data/Cityscapes/autolabelled",   # config.py:80-81
+        COARSE_BOOST_CLASSES=None,   # config.py:104, 249-251 (--coarse_boost_classes): cityscapes.py's file discovery reads it
+        CUSTOM_COARSE_PROB=None,     # config.py:107, 234-235 (--custom_coarse_prob): labels below this confidence are ignored
+        MASK_OUT_CITYSCAPES=False,   # config.py:108, 300-301 (--mask_out_cityscapes): the drop mask of auto-labelled items
     )
     c.DATASET_INST = None            # config.py:381 (update_dataset_inst): colorize_mask / id_to_trainid of ImageDumper
     c.RESULT_DIR = None              # config.py:64, 298 (args.result_dir): where ImageDumper writes
@@ -63,7 +69,7 @@ def _defaults():
     c.BORDER_WINDOW = 1              # config.py:58 (half width of the label relaxation window)
     c.REDUCE_BORDER_EPOCH = -1       # config.py:60 (the 'scl-poly' LR schedule switches there)
     c.STRICTBORDERCLASS = None       # config.py:62 (classes whose pixels are never relaxed)
-    c.DROPOUT_COARSE_BOOST_CLASSES = None   # config.py:350-353 (the auto-labelled branch of the centroid pass: not built)
+    c.DROPOUT_COARSE_BOOST_CLASSES = None   # config.py:350-353 (--custom_coarse_dropout_classes): datasets/autolabel.py
     return c
 
 
@@ -87,7 +93,8 @@ def sync_from_reference(ref_cfg):
         if hasattr(ref_cfg, k):
             cfg[k] = getattr(ref_cfg, k)
     for k in ("NAME", "CLASS_UNIFORM_PCT", "CLASS_UNIFORM_TILE", "CLASS_UNIFORM_BIAS", "CENTROID_ROOT", "TRANSLATE_AUG_FIX",
-              "MEAN", "STD"):
+              "MEAN", "STD", "CITYSCAPES_DIR", "CITYSCAPES_CUSTOMCOARSE", "COARSE_BOOST_CLASSES", "CUSTOM_COARSE_PROB",
+              "MASK_OUT_CITYSCAPES"):
         if hasattr(ref_cfg.DATASET, k):         # (CLASS_UNIFORM_BIAS exists only after assert_and_infer_cfg)
             cfg.DATASET[k] = getattr(ref_cfg.DATASET, k)
     cfg.DROPOUT_COARSE_BOOST_CLASSES = getattr(ref_cfg, "DROPOUT_COARSE_BOOST_CLASSES", None)

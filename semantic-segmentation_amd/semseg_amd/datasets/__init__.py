@@ -10,3 +10,4 @@ from .transforms import AugmentParams, RandAugment, rand_augment   # noqa: F401
 from .transforms import CropPlan, RandomSizeAndCrop, pad_u8, resize_image_bicubic   # noqa: F401
 from .uniform import (build_centroids, build_epoch, calc_tile_locations, class_centroids, class_centroids_all,   # noqa: F401
                       class_centroids_image, pooled_class_centroids_all, random_sampling)
+from .autolabel import label_plan, label_steps, prepare_labels, prob_cut, read_labels   # noqa: F401

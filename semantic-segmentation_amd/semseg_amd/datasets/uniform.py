@@ -11,8 +11,11 @@ copy.  The sampling itself (random_sampling, build_epoch) stays on the host and 
 reference does, so a seeded run draws the same epoch.  The centroid cache (build_centroids) has the reference's file
 name and JSON text: a cache written by either side loads in the other.
 
-Not built: the `refinement` / gtCoarse / cfg.DROPOUT_COARSE_BOOST_CLASSES branch of class_centroids_image
-(uniform.py:104-120), which raises NotImplementedError."""
+Auto-labelled items (`refinement` in the label path with cfg.DROPOUT_COARSE_BOOST_CLASSES set, uniform.py:104-120): the
+gtCoarse map is decoded beside the label, in the same thread pool and the same size batching, the id2trainid loop with
+the gtCoarse merge of the boosted classes runs on the device (datasets/autolabel.py, prepare_labels(mode="original")) and
+the centroid pass then takes its result without a table.  Such an item whose path does not contain
+cfg.DATASET.CITYSCAPES_CUSTOMCOARSE has no gtCoarse map in the reference either (a NameError there) and is refused."""
 import json
 import os
 from collections import defaultdict
@@ -22,6 +25,7 @@ import numpy as np
 import torch
 
 from ..config import cfg
+from .autolabel import coarse_path, label_steps, prepare_labels
 
 MAX_DECODE_WORKERS = 16      # host threads that decode PNGs (the reference's pool has 80, uniform.py:147)
 BATCH_ITEMS = 16             # label maps decoded ahead and, where their sizes agree, processed in one launch
@@ -90,8 +94,14 @@ def class_centroids(labels_u8_cuda, tile_size, num_classes, id2trainid=None):
     return out[0] if squeeze else out
 
 
+def _auto_labelled(label_fn, id2trainid):
+    """Whether the id2trainid loop of uniform.py:113-121 may merge gtCoarse pixels into this item's classes."""
+    return bool(id2trainid) and "refinement" in label_fn and cfg.DROPOUT_COARSE_BOOST_CLASSES is not None
+
+
 def _check_item(label_fn):
-    if "refinement" in label_fn and cfg.DROPOUT_COARSE_BOOST_CLASSES is not None:
+    if ("refinement" in label_fn and cfg.DROPOUT_COARSE_BOOST_CLASSES is not None
+            and cfg.DATASET.CITYSCAPES_CUSTOMCOARSE not in label_fn):
         raise NotImplementedError("the auto-labelled (refinement / gtCoarse / DROPOUT_COARSE_BOOST_CLASSES) branch of the "
                                   "centroid pass is not implemented: %s" % label_fn)
 
@@ -102,6 +112,26 @@ def _decode(label_fn):
     if mask.dtype != np.uint8 or mask.ndim != 2:
         raise ValueError("%s: a label map is one 8-bit channel, not %s %r" % (label_fn, mask.dtype, mask.shape))
     return mask
+
+
+def _decode_pair(fns):
+    """(label map, gtCoarse map or None) of (label_fn, gtCoarse file or None): one job of the decoding pool."""
+    label_fn, coarse_fn = fns
+    mask = _decode(label_fn)
+    if coarse_fn is None:
+        return mask, None
+    coarse = _decode(coarse_fn)
+    if coarse.shape != mask.shape:
+        raise ValueError("%s is %r, the label map %s %r" % (coarse_fn, coarse.shape, label_fn, mask.shape))
+    return mask, coarse
+
+
+def _merged_centroids(labels, coarse, tile_size, num_classes, id2trainid):
+    """class_centroids of auto-labelled maps: the loop of uniform.py:112-121 with its gtCoarse merge first (the hit taken
+    against the untouched map, the last hitting step wins), then the centroid pass without a table."""
+    steps = label_steps(id2trainid, cfg.DROPOUT_COARSE_BOOST_CLASSES)
+    merged = prepare_labels(labels, coarse if any(steps[2::3]) else None, None, steps, "original")
+    return class_centroids(merged, tile_size, num_classes, None)
 
 
 def _as_dict(item, table):
@@ -115,19 +145,27 @@ def _as_dict(item, table):
     return centroids
 
 
-def class_centroids_image(item, tile_size, num_classes, id2trainid, labels=None):
+def class_centroids_image(item, tile_size, num_classes, id2trainid, labels=None, coarse=None):
     """item = (image_fn, label_fn) -> {class_id: [(image_fn, label_fn, (x, y), class_id), ...]} (uniform.py:84-135).
-    labels: the decoded label map as a uint8 device tensor [H,W], if the caller has it; else label_fn is read."""
+    labels: the decoded label map as a uint8 device tensor [H,W], if the caller has it; else label_fn is read.  coarse:
+    likewise the gtCoarse map of an auto-labelled item."""
     _check_item(item[1])
+    auto = _auto_labelled(item[1], id2trainid)
     if labels is None:
         labels = torch.from_numpy(_decode(item[1])).to(DEVICE)
-    return _as_dict(item, class_centroids(labels, tile_size, num_classes, id2trainid).cpu().numpy())
+    if not auto:
+        return _as_dict(item, class_centroids(labels, tile_size, num_classes, id2trainid).cpu().numpy())
+    if coarse is None:
+        coarse = torch.from_numpy(_decode_pair((item[1], coarse_path(item[1])))[1]).to(labels.device)
+    return _as_dict(item, _merged_centroids(labels, coarse, tile_size, num_classes, id2trainid).cpu().numpy())
 
 
 def pooled_class_centroids_all(items, num_classes, id2trainid, tile_size=1024):
     """items: [(image_fn, label_fn), ...] -> {class_id: [...]} over all of them, each class's list in item order as
     pool.map keeps it (uniform.py:138-164).  BATCH_ITEMS maps are decoded at a time on at most MAX_DECODE_WORKERS host
-    threads; those of one size go to the device as one tensor, through one call, and come back in one copy."""
+    threads; those of one size go to the device as one tensor, through one call, and come back in one copy.  The gtCoarse
+    map of an auto-labelled item is decoded by the same job as its label; auto-labelled maps of one size form a group of
+    their own, which goes through prepare_labels and then through the centroid call without a table."""
     items = [tuple(it) for it in items]
     for _, label_fn in items:
         _check_item(label_fn)
@@ -137,14 +175,20 @@ def pooled_class_centroids_all(items, num_classes, id2trainid, tile_size=1024):
     with ThreadPoolExecutor(max_workers=min(MAX_DECODE_WORKERS, BATCH_ITEMS, len(items))) as pool:
         for lo in range(0, len(items), BATCH_ITEMS):
             batch = items[lo:lo + BATCH_ITEMS]
-            masks = list(pool.map(_decode, [label_fn for _, label_fn in batch]))
+            auto = [_auto_labelled(label_fn, id2trainid) for _, label_fn in batch]
+            masks = list(pool.map(_decode_pair, [(label_fn, coarse_path(label_fn) if a else None)
+                                                 for (_, label_fn), a in zip(batch, auto)]))
             by_size = defaultdict(list)
-            for i, m in enumerate(masks):
-                by_size[m.shape].append(i)
+            for i, (m, _) in enumerate(masks):
+                by_size[(m.shape, auto[i])].append(i)
             tables = [None] * len(batch)
-            for idx in by_size.values():
-                stacked = torch.from_numpy(np.stack([masks[i] for i in idx])).to(DEVICE)
-                host = class_centroids(stacked, tile_size, num_classes, id2trainid).cpu().numpy()
+            for (_, merged), idx in by_size.items():
+                stacked = torch.from_numpy(np.stack([masks[i][0] for i in idx])).to(DEVICE)
+                if merged:
+                    coarse = torch.from_numpy(np.stack([masks[i][1] for i in idx])).to(DEVICE)
+                    host = _merged_centroids(stacked, coarse, tile_size, num_classes, id2trainid).cpu().numpy()
+                else:
+                    host = class_centroids(stacked, tile_size, num_classes, id2trainid).cpu().numpy()
                 for j, i in enumerate(idx):
                     tables[i] = host[j]
             for item, table in zip(batch, tables):
