@@ -806,6 +806,24 @@ int ssa_relax_nll_finalize(const double* acc, const int64_t* stats, int B, int H
 int ssa_relax_nll_bwd(const float* logits, int ld, const unsigned long long* sets, const float* w, const int64_t* stats,
                       int B, int H, int W, int C, const float* upstream, float* dlogits, void* stream);
 
+/* Boundary F-score: eval_mask_boundary, utils/f_boundary.py:61-92, over db_eval_boundary (:110-173) and the full-size
+ * branch of seg2bmap (:175-233), for every class of every image in two launches.  pred_u8 [B][H][W] uint8 (the `pred`
+ * bytes of ssa_eval_tail), gts [B][H][W] int64 or (gts_u8) uint8.  A pixel whose ground truth equals ignore_label is
+ * cleared in BOTH maps (:133-134); a ground-truth label outside [0, C) that is not ignore_label, and a prediction byte
+ * >= C, belong to no class.  Class c is a boundary class of a pixel iff c occurs in its 2 x 2 quad {p, e, s, se} and
+ * not every member is c (:209-217); on the last row the quad is the pair {p, e}, on the last column {p, s}, and the
+ * bottom-right pixel is no boundary (:218-220).  radius = disk(bound_pix) of :127-128,142-143 as an integer, taken by
+ * the host: a boundary pixel is matched iff the other map has a boundary pixel of its class at dx^2 + dy^2 <=
+ * radius^2, positions outside the image being empty.
+ * counts int64 [B][C][4] = {n_fg, n_gt, fg_match, gt_match} (:146-151,164-165), cleared by the first launch: exact
+ * integer sums.  Precision, recall and F (:154-171) are the host's, in float64.
+ * workspace: 8 * B * H * W bytes (ssa_fboundary_workspace_bytes), 4-byte aligned: both boundary maps as four class
+ * bytes per pixel, 0xFF = empty.  1 <= C <= 254 and 0 <= radius <= 32, otherwise SSA_EUNSUPPORTED; B <= 65535.      */
+int ssa_fboundary_workspace_bytes(int B, int H, int W, size_t* bytes);
+int ssa_fboundary_counts(const unsigned char* pred_u8, const void* gts, int gts_u8, int B, int H, int W, int C,
+                         int ignore_label, int radius, int64_t* counts, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* Tail of the input pipeline on the device: joint crop window + optional
  * horizontal flip of the cropped pair (transforms/joint_transforms.py:276-281
  * RandomHorizontallyFlip after the crop transforms), then for the image ToTensor + Normalize

@@ -243,6 +243,8 @@ _SIGS = {
     "ssa_relax_nll_fwd": ([_P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ssa_relax_nll_finalize": ([_P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ssa_relax_nll_bwd": ([_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P], c_int),
+    "ssa_fboundary_workspace_bytes": ([c_int, c_int, c_int, POINTER(c_size_t)], c_int),
+    "ssa_fboundary_counts": ([_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P], c_int),
     "ssa_image_u8_crop_flip_normalize": ([_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P],
                                          c_int),
     "ssa_resample_u8": ([_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P], c_int),

@@ -14,6 +14,8 @@ time, so `train.py`, `config.py` and `scripts/*.yml` run unchanged:
   utils.trnval_utils (eval_minibatch, flip_tensor, resize_tensor; validate_topn raises) -- only with
   install(device_eval_tail=True)
         -> semseg_amd.utils.eval_tail    (train.py:44; the evaluation tail in one kernel instead of on the host)
+  utils.f_boundary (eval_mask_boundary) -- only with install(device_f_boundary=True)
+        -> semseg_amd.utils.f_boundary   (the boundary F-score of utils/misc.py's `mf_score`, on the device)
   utils.misc.ImageDumper -- only with install(device_dumper=True)
         -> semseg_amd.utils.dumper.ImageDumper   (train.py:43; the per-pixel work of dump() in one kernel)
   apex.parallel.SyncBatchNorm / DistributedDataParallel, apex.amp
@@ -79,13 +81,15 @@ def _select_storage_from_argv():
         os.environ["SSA_ACT_DTYPE"] = "fp16"
 
 
-def install(replace_apex=True, device_eval_tail=False, device_dumper=False):
+def install(replace_apex=True, device_eval_tail=False, device_dumper=False, device_f_boundary=False):
     """device_eval_tail=True also registers `utils.trnval_utils` (train.py:44 imports eval_minibatch and validate_topn
     from there): eval_minibatch with its tail on the device (semseg_amd/utils/eval_tail.py).  Off by default.
     device_dumper=True (off by default; implies device_eval_tail) puts semseg_amd.utils.dumper.ImageDumper where
     train.py:43 imports the class from -- the attribute `ImageDumper` of the reference's own `utils.misc`, which is
     imported for that and keeps everything else it holds -- and makes the registered eval_minibatch leave its assets
-    on the device (assets_on_device=True), where that class picks them up."""
+    on the device (assets_on_device=True), where that class picks them up.
+    device_f_boundary=True (off by default) registers semseg_amd.utils.f_boundary as `utils.f_boundary`: eval_mask_boundary
+    with the reference's signature and return value, computed by the kernels of csrc/fboundary.hip."""
     _select_storage_from_argv()
     from . import nn as snn, parallel, network, loss
     from .network import ocrnet, hrnetv2, ocr_utils, utils as nutils, mynn, deepv3, mscale, mscale2, attnscale
@@ -130,6 +134,11 @@ def install(replace_apex=True, device_eval_tail=False, device_dumper=False):
             from .utils import dumper
             importlib.import_module("utils.misc").ImageDumper = dumper.ImageDumper
         sys.modules["utils.trnval_utils"] = tv
+    if device_f_boundary:
+        import importlib
+        fb = importlib.import_module(__package__ + ".utils.f_boundary")
+        fb._SYNC_CFG[0] = True
+        sys.modules["utils.f_boundary"] = fb
     return network, loss
 
 

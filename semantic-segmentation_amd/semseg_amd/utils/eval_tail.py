@@ -157,7 +157,7 @@ def _to_host(tensors):
     return outs
 
 
-def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx, assets_on_device=False):
+def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx, assets_on_device=False, boundary=None):
     """utils/trnval_utils.py:82-198 with its tail on the device.  Same arguments, same returns: (assets, _iou_acc) with
     `predictions` int64 ndarray [B,H,W], `prob_mask` CPU fp32 tensor, `err_mask` int ndarray (calc_metrics), every
     `pred_*` of the last pass as int64 ndarray at its own size, every `attn_*` passed through, `_iou_acc` int64 [C,C];
@@ -168,7 +168,9 @@ def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx, 
     package's CrossEntropyLoss2d with the dataset's ignore label; any other criterion is called on the averaged tensor.
     assets_on_device=True (what `dropin.install(device_dumper=True)` passes): the assets stay where the tail wrote them,
     for utils/dumper.py -- `predictions`, `err_mask` and every `pred_*` as device uint8, `prob_mask` as device fp32, the
-    `attn_*` untouched, and the uploaded batch under `input_images` / `gt_images`; only the counters come back."""
+    `attn_*` untouched, and the uploaded batch under `input_images` / `gt_images`; only the counters come back.
+    boundary: a utils.f_boundary.BoundaryMeter, fed the final `pred` bytes and the ground truth on the device when
+    calc_metrics (the reference's `mf_score`, which its own loop never fills); None leaves every path as it is."""
     from ..config import cfg
     from ..loss.criteria import CrossEntropyLoss2d
     if _SYNC_CFG[0] and "config" in sys.modules and hasattr(sys.modules["config"], "assert_and_infer_cfg"):
@@ -211,6 +213,8 @@ def eval_minibatch(data, net, criterion, val_loss, calc_metrics, args, val_idx, 
         res = eval_tail(srcs, src_flips, C, gts=gts, ignore_label=ignore, n_scales=len(scales), n_flips=len(flips),
                         want=("pred", "prob", "err") if calc_metrics else ("pred", "prob"),
                         avg=bool(calc_metrics) and not fused)
+        if boundary is not None and calc_metrics:
+            boundary.update(res.pred, gts)
         loss = None
         if calc_metrics and not fused:
             loss = criterion(res.avg, gts).item()
