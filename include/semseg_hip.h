@@ -572,6 +572,44 @@ int ssa_gconv3x3_bwd_plan(const ssa_gconv_desc* d, size_t* ws_bytes);
 int ssa_gconv3x3_bwd(const ssa_gconv_desc* d, const void* x, const void* dy, int lddy, const float* w, void* dx,
                      int lddx, float* dw, int accumulate, void* ws, void* stream);
 
+/* ----------------------------------------------- rectangular-dilation 3x3 conv ----
+ * nn.Conv2d(Cin, Cout, 3, stride = 1, padding = (dil_h, dil_w), dilation = (dil_h, dil_w), bias = False): the five convs
+ * of the Dense Prediction Cell (dpc_conv / DPC, network/utils.py:249-260; rates (1,6) (18,15) (6,21) (1,1) (6,3), doubled at
+ * output stride 8).  ssa_conv_desc has one dilation; this family has a descriptor and entry points of its own
+ * (csrc/conv_dil.hip).  NHWC 16-bit, fp32 accumulate on MFMA.  x [B,H,W,Cin] with pixel stride ldx >= Cin, y [B,H,W,Cout]
+ * with ldy >= Cout, both strides % 8, both pointers 16-byte aligned: x and y may be disjoint channel slices of ONE
+ * allocation (the cell's convs write their slices of the concatenated output and read `a` back out of it).
+ * Supported: Cin % 64 == 0 and Cout % 64 == 0, any B, H, W >= 1, any dil_h, dil_w >= 1 (dil >= H or W included: the
+ * off-centre taps of that axis are then outside everywhere).  Other channel counts: SSA_EUNSUPPORTED (-2).  A bad
+ * descriptor (NULL, B / H / W / Cin / Cout < 1, dil < 1, ldx < Cin, ldy < Cout, a stride % 8 != 0, 2^31 pixels or more)
+ * or a NULL / misaligned operand: SSA_EINVAL (-1).  Nothing is launched in either case.
+ * A tap reads zero wherever iy = oy + (kh-1) dil_h or ix = ox + (kw-1) dil_w leaves [0,H) x [0,W) of its own image; a
+ * tap that is outside for a workgroup's whole 64-pixel tile costs that workgroup nothing.                          */
+typedef struct ssa_dilconv_desc {
+  int B, H, W, Cin, ldx;   /* x [B,H,W,Cin], pixel stride ldx   */
+  int Cout, ldy;           /* y [B,H,W,Cout], pixel stride ldy  */
+  int dil_h, dil_w;        /* dilation = padding, per axis      */
+} ssa_dilconv_desc;
+int ssa_dilconv3x3_supported(const ssa_dilconv_desc* d);
+/* Forward, 16-bit output.  w_frag: ssa_pack_filter mode 2 of the OIHW parameter (cin_pad = Cin, Kpad = 9 Cin).  stats
+ * (optional): the BatchNorm partial sums of the ROUNDED outputs with ssa_conv2d_tile's contract --
+ * [ssa_bn_stat_replicas()][2][Cout] fp64, ACCUMULATED (caller clears).
+ * DATA GRADIENT: with stride 1 and padding = dilation on both axes the data gradient is the same conv with the
+ * flipped, transposed filter, so this entry point serves both: x = dy [B,H,W,Cout_fwd], y = dx [B,H,W,Cin_fwd], the
+ * descriptor's Cin / Cout exchanged, w_frag = ssa_pack_filter mode 3 (cout_pad = Cout_fwd, Kpad = 9 Cout_fwd), stats NULL.
+ * Group-aware: inside an ssa_group bracket several problems (the cell's b, c, d; their three data gradients) share
+ * one launch.                                                                                                       */
+int ssa_dilconv3x3(const ssa_dilconv_desc* d, const void* x, const void* w_frag, void* y, double* stats, void* stream);
+/* Weight gradient: dw [Cout][Cin][3][3] fp32 (the parameter's OIHW layout) = sum over pixels of dy x; overwritten, or
+ * added to when accumulate != 0 (dw = the layer's slice of the step's gradient arena, ssa_gconv3x3_bwd's rule).  x as in
+ * the descriptor; dy [B,H,W,Cout] with pixel stride lddy (the descriptor's ldy is not read).  The sum over pixels has
+ * a fixed order: workgroups split the pixel axis into *nsplit parts, write fp32 partials to ws (*ws_bytes of the plan,
+ * 16-byte aligned, every byte of it overwritten) and a second launch adds the parts in order -- no floating-point
+ * atomics.  Not group-aware (two dependent launches).                                                            */
+int ssa_dilconv3x3_wgrad_plan(const ssa_dilconv_desc* d, int* nsplit, size_t* ws_bytes);
+int ssa_dilconv3x3_wgrad(const ssa_dilconv_desc* d, const void* x, const void* dy, int lddy, float* dw, int accumulate,
+                         void* ws, void* stream);
+
 /* ------------------------------------------------- squeeze-and-excitation gate ----
  * z = relu(se_module(y) + residual), se_module(y) = y * sigmoid(fc2(relu(fc1(avg_pool(y))))): SEModule.forward and the
  * tail of Bottleneck.forward (network/SEresnext.py:84-91, 115-116).  y, r, z, dz, dy, dr: NHWC 16-bit [B,HW,C] with

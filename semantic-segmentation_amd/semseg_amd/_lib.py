@@ -83,6 +83,11 @@ class GConvDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("B", "H", "W", "C", "G", "ldx", "Ho", "Wo", "ldy", "stride", "dil")]
 
 
+class DilConvDesc(ctypes.Structure):
+    """Mirror of ssa_dilconv_desc."""
+    _fields_ = [(n, c_int) for n in ("B", "H", "W", "Cin", "ldx", "Cout", "ldy", "dil_h", "dil_w")]
+
+
 class JitterProgram(ctypes.Structure):
     """Mirror of ssa_jitter_program (36 bytes)."""
     _fields_ = [("n_ops", c_int), ("op", c_int * 4), ("factor", c_float * 3), ("hue_byte", c_int)]
@@ -193,6 +198,10 @@ _SIGS = {
     "ssa_gconv3x3": ([POINTER(GConvDesc), _P, _P, _P, _P, _P], c_int),
     "ssa_gconv3x3_bwd_plan": ([POINTER(GConvDesc), POINTER(c_size_t)], c_int),
     "ssa_gconv3x3_bwd": ([POINTER(GConvDesc), _P, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P], c_int),
+    "ssa_dilconv3x3_supported": ([POINTER(DilConvDesc)], c_int),
+    "ssa_dilconv3x3": ([POINTER(DilConvDesc), _P, _P, _P, _P, _P], c_int),
+    "ssa_dilconv3x3_wgrad_plan": ([POINTER(DilConvDesc), POINTER(c_int), POINTER(c_size_t)], c_int),
+    "ssa_dilconv3x3_wgrad": ([POINTER(DilConvDesc), _P, _P, c_int, _P, c_int, _P, _P], c_int),
     "ssa_se_plan": ([c_int, c_long, c_int, c_int, POINTER(c_size_t)], c_int),
     "ssa_se_squeeze_gate": ([_P, c_int, c_int, c_long, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
     "ssa_se_apply": ([_P, c_int, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, _P], c_int),

@@ -29,7 +29,7 @@ import weakref
 
 import torch
 
-from ._lib import lib, check, ConvDesc, DwConvDesc, GConvDesc, PackJob, BnUpdateJob, BnEvalJob, ProfileRec
+from ._lib import lib, check, ConvDesc, DwConvDesc, GConvDesc, DilConvDesc, PackJob, BnUpdateJob, BnEvalJob, ProfileRec
 
 from ._lib import ACT as _ACT_NAME     # storage format of the activations = the library build (SSA_ACT_DTYPE)
 ACT_DTYPE = torch.float16 if _ACT_NAME == "fp16" else torch.bfloat16
@@ -2417,6 +2417,150 @@ class GConv3x3Fn(torch.autograd.Function):
         if need_dw and not param and dw.dtype != weight.dtype:
             dw = dw.to(weight.dtype)
         return dx, (None if param or not need_dw else dw), None, None, None, None
+
+
+# --------------------------------------------------------------------------
+# 3x3 conv with a dilation per axis (network/utils.py:249-260: the five convs of the Dense Prediction Cell)
+# --------------------------------------------------------------------------
+def _dil_desc(B, H, W, Cin, ldx, Cout, ldy, dil):
+    """The descriptor of csrc/conv_dil.hip; a shape its kernels are not built for raises here, before anything is
+    launched (there is no other route for a rectangular dilation)."""
+    d = DilConvDesc(B, H, W, Cin, ldx, Cout, ldy, int(dil[0]), int(dil[1]))
+    if not lib().ssa_dilconv3x3_supported(ctypes.byref(d)):
+        raise NotImplementedError("rectangular-dilation 3x3 conv: B x H x W = %d x %d x %d, %d -> %d channels (strides %d, "
+                                  "%d), dilation %s is not supported (channel counts must be multiples of 64)" %
+                                  (B, H, W, Cin, Cout, ldx, ldy, tuple(dil)))
+    return d
+
+
+class DilConvGroupFn(torch.autograd.Function):
+    """nn.Conv2d(Cin, Cout, 3, stride 1, padding = dilation = (dil_h, dil_w), bias = False) on NHWC for N independent
+    problems (b, c, d of the cell: three rate pairs on one input), issued inside ONE group bracket: one launch forward,
+    one launch for the data gradients.  spec[i] = ((dil_h, dil_w), want_stats); tensors = (x_0, w_0, x_1, w_1, ...), x 16-bit
+    (a channel slice of a wider buffer is read in place), weight OIHW fp32.  want_stats: the epilogue takes the batch
+    statistics of the stored output and leaves them for the BatchNorm that consumes it (_PENDING_STATS, as GConv3x3Fn).
+    Backward: the data gradient is the same kernel on the flipped, transposed filter (pack mode 3); the weight gradient
+    (ssa_dilconv3x3_wgrad: partials + an ordered reduce) is added into a parameter's gradient-arena slice."""
+
+    @staticmethod
+    def forward(ctx, spec, *tensors):
+        n = len(spec)
+        xs, lds, ws, ys = [], [], [], []
+        for i in range(n):
+            w = tensors[2 * i + 1]
+            assert w.dim() == 4 and tuple(w.shape[2:]) == (3, 3), tuple(w.shape)
+            x, ldx = _act_operand(tensors[2 * i], w.shape[1])
+            xs.append(x)
+            lds.append(ldx)
+            ws.append(w)
+        with group():
+            for i in range(n):
+                dil, want_stats = spec[i]
+                B, H, W, Cin = xs[i].shape
+                Cout = ws[i].shape[0]
+                d = _dil_desc(B, H, W, Cin, lds[i], Cout, Cout, dil)
+                wp, _ = _packed_filter(ws[i], 2, Cin, 0)
+                stats = _ARENA.take(stat_replicas() * 2 * Cout, xs[i].device) if want_stats else None
+                y = torch.empty((B, H, W, Cout), dtype=ACT_DTYPE, device=xs[i].device)
+                _note(18.0 * Cin * y.numel(), 2.0 * (xs[i].numel() + y.numel() + 9 * Cin * Cout))
+                check(lib().ssa_dilconv3x3(ctypes.byref(d), _p(xs[i]), _p(wp), _p(y), _p(stats), _s()), "ssa_dilconv3x3")
+                if stats is not None:
+                    _PENDING_STATS[y.data_ptr()] = (stats, stat_replicas())      # picked up by _bn_train_fwd
+                ys.append(y)
+        ctx.save_for_backward(*(xs + ws))
+        ctx.meta = (spec, lds)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        spec, lds = ctx.meta
+        n = len(spec)
+        xs, ws = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        prep = [None if dy is None else _dz_bf16(dy, ws[i].shape[0]) for i, dy in enumerate(dys)]
+        dxs = [None] * n
+        with group():
+            for i in range(n):
+                if prep[i] is None or not ctx.needs_input_grad[1 + 2 * i]:
+                    continue
+                B, H, W, Cin = xs[i].shape
+                Cout = ws[i].shape[0]
+                dyb, lddy = prep[i]
+                d = _dil_desc(B, H, W, Cout, lddy, Cin, Cin, spec[i][0])
+                wp, _ = _packed_filter(ws[i], 3, 0, Cout)
+                dxs[i] = torch.empty((B, H, W, Cin), dtype=ACT_DTYPE, device=dyb.device)
+                _note(18.0 * Cout * dxs[i].numel(), 2.0 * (dyb.numel() + dxs[i].numel() + 9 * Cin * Cout))
+                check(lib().ssa_dilconv3x3(ctypes.byref(d), _p(dyb), _p(wp), _p(dxs[i]), None, _s()), "ssa_dilconv3x3")
+        grads = [None]
+        for i in range(n):
+            dw = None
+            if prep[i] is not None and ctx.needs_input_grad[2 + 2 * i]:
+                B, H, W, Cin = xs[i].shape
+                w = ws[i]
+                Cout = w.shape[0]
+                dyb, lddy = prep[i]
+                d = _dil_desc(B, H, W, Cin, lds[i], Cout, Cout, spec[i][0])
+                param = _is_param(w)
+                dw = _GRADS.slot(w) if param else torch.empty(w.shape, dtype=torch.float32, device=dyb.device)
+                nsplit, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+                check(lib().ssa_dilconv3x3_wgrad_plan(ctypes.byref(d), ctypes.byref(nsplit), ctypes.byref(nbytes)),
+                      "ssa_dilconv3x3_wgrad_plan")
+                # the splits' partial sums: written before they are read, freed with this node (DwConv3x3Fn's scheme)
+                part = torch.empty((nbytes.value // 4,), dtype=torch.float32, device=dyb.device)
+                _note(18.0 * Cin * Cout * B * H * W, 2.0 * (xs[i].numel() + dyb.numel()) + 8.0 * part.numel())
+                check(lib().ssa_dilconv3x3_wgrad(ctypes.byref(d), _p(xs[i]), _p(dyb), lddy, _p(dw), int(param), _p(part),
+                                                 _s()), "ssa_dilconv3x3_wgrad")
+                if param:
+                    dw = None
+                elif dw.dtype != w.dtype:
+                    dw = dw.to(w.dtype)
+            grads += [dxs[i], dw]
+        return tuple(grads)
+
+
+def slices_of_one_buffer(tensors):
+    """The tensors are, in order, ALL the channel slices of one NHWC buffer (what ops.cat_slots hands out): same storage,
+    same strides, offsets one behind the other, pixels exactly as wide as the slices together."""
+    a = tensors[0]
+    if not all(t.dim() == 4 and t.dtype == a.dtype and t.shape[:3] == a.shape[:3] and t.stride() == a.stride()
+               for t in tensors):
+        return False
+    ld = sum(t.shape[3] for t in tensors)
+    try:
+        base = a.untyped_storage().data_ptr()
+        same = all(t.untyped_storage().data_ptr() == base for t in tensors)
+    except Exception:       # noqa: BLE001
+        return False
+    if not same or a.stride(3) != 1 or a.stride(2) != ld or a.stride(1) != a.shape[2] * ld or \
+            a.stride(0) != a.shape[1] * a.shape[2] * ld:
+        return False
+    off = a.storage_offset()
+    for t in tensors:
+        if t.storage_offset() != off:
+            return False
+        off += t.shape[3]
+    return True
+
+
+class CatSlotsFn(torch.autograd.Function):
+    """CatViewFn for any number of slices: torch.cat(tensors, dim=3) of tensors that already are the neighbouring
+    channel slices of one buffer -- the dense view of that buffer, no copy; backward = the slices of the gradient.  The
+    READ-ONLY contract of CatViewFn holds.  Its consumer is the bottleneck conv behind the Dense Prediction Cell."""
+
+    @staticmethod
+    def forward(ctx, *tensors):
+        ctx.widths = [t.shape[3] for t in tensors]
+        a = tensors[0]
+        B, H, W, _ = a.shape
+        ld = sum(ctx.widths)
+        return a.detach().as_strided((B, H, W, ld), (H * W * ld, W * ld, ld, 1), a.storage_offset())
+
+    @staticmethod
+    def backward(ctx, g):
+        out, off = [], 0
+        for w in ctx.widths:
+            out.append(g[..., off:off + w])
+            off += w
+        return tuple(out)
 
 
 def image_to_nhwc(images, out_hw=None, cpad=16, align_corners=False):

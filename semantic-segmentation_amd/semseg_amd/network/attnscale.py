@@ -40,10 +40,10 @@ def _scale_attn_head(num_scales, bn_head, sigmoid):
 
 
 class _ASBase(_Base):
-    def _build(self, num_classes, trunk, criterion, num_scales, bn_head, sigmoid):
+    def _build(self, num_classes, trunk, criterion, num_scales, bn_head, sigmoid, use_dpc=False):
         self.criterion = criterion
         self.backbone, s2_ch, _s4_ch, high_level_ch = get_trunk(trunk)
-        self.aspp, aspp_out_ch = get_aspp(high_level_ch, bottleneck_ch=256, output_stride=8)
+        self.aspp, aspp_out_ch = get_aspp(high_level_ch, bottleneck_ch=256, output_stride=8, dpc=use_dpc)
         self.bot_fine = Conv2d(s2_ch, 48, kernel_size=1, bias=False)
         self.bot_aspp = Conv2d(aspp_out_ch, 256, kernel_size=1, bias=False)
         self.final = nn.Sequential(
@@ -112,11 +112,10 @@ class ASDV3P(_ASBase):
     def __init__(self, num_classes, trunk="resnet-50", criterion=None, use_dpc=False, fuse_aspp=False,
                  attn_2b=False, bn_head=False):
         super().__init__()
-        assert not use_dpc
         assert cfg.MODEL.N_SCALES is not None
         self.fuse_aspp, self.attn_2b = fuse_aspp, attn_2b
         self.scales = sorted(cfg.MODEL.N_SCALES)
-        self._build(num_classes, trunk, criterion, len(self.scales), bn_head, sigmoid=False)
+        self._build(num_classes, trunk, criterion, len(self.scales), bn_head, sigmoid=False, use_dpc=use_dpc)
 
     def _forward_fused(self, inputs):
         B = ops.backend()
@@ -152,12 +151,11 @@ class ASDV3P_Paired(_ASBase):
     def __init__(self, num_classes, trunk="resnet-50", criterion=None, use_dpc=False, fuse_aspp=False,
                  attn_2b=False, bn_head=False):
         super().__init__()
-        assert not use_dpc
         assert cfg.MODEL.N_SCALES is not None
         self.fuse_aspp, self.attn_2b = fuse_aspp, attn_2b
         self.trn_scales = (0.5, 1.0)
         self.inf_scales = sorted(cfg.MODEL.N_SCALES)
-        self._build(num_classes, trunk, criterion, 2, bn_head, sigmoid=True)
+        self._build(num_classes, trunk, criterion, 2, bn_head, sigmoid=True, use_dpc=use_dpc)
 
     def _forward_paired(self, inputs, scales):
         B = ops.backend()

@@ -10,7 +10,7 @@ from torch import nn
 
 from .. import ops
 from ..config import cfg
-from ..nn import Conv2d, Norm2d, conv_bn, initialize_weights
+from ..nn import BatchNorm2d, Conv2d, DilConv2d, Norm2d, conv_bn, initialize_weights
 from .mynn import Upsample
 from .utils import get_trunk
 
@@ -46,9 +46,62 @@ class AtrousSpatialPyramidPoolingModule(nn.Module):
         return B.cat(outs)
 
 
+def dpc_conv(in_dim, reduction_dim, dil, separable):
+    """network/utils.py:249-260: 3x3 conv with dilation = padding = (dil_h, dil_w) -> BatchNorm -> ReLU.  The reference
+    builds this BatchNorm with nn.BatchNorm2d, NOT Norm2d: under --syncbn the cell's statistics stay local to the rank.
+    Mirrored here with semseg_amd.nn.BatchNorm2d."""
+    if separable:
+        raise NotImplementedError("dpc_conv(separable=True): get_aspp never sets it; there is no depthwise kernel with a "
+                                  "dilation per axis")
+    return nn.Sequential(DilConv2d(in_dim, reduction_dim, kernel_size=3, dilation=dil, padding=dil, bias=False),
+                         BatchNorm2d(reduction_dim), nn.ReLU(inplace=True))
+
+
+class DPC(nn.Module):
+    """network/utils.py:263-298: the Dense Prediction Cell of "Searching for Efficient Multi-Scale Architectures for
+    Dense Prediction".  Five 3x3 convs whose dilation differs per axis -- (dil_h, dil_w) = (1,6) (18,15) (6,21) (1,1) (6,3),
+    doubled at output stride 8 -- wired a(x), b(a), c(a), d(a), e(b) and concatenated in the order a, b, c, d, e.  Children
+    a .. e = Sequential(conv, BatchNorm, ReLU) and `drop`: the reference's state-dict keys.  The BatchNorms are local
+    (nn.BatchNorm2d in the reference, not Norm2d; see dpc_conv).
+
+    On the HIP backend the five layers write their slices of ONE [B,H,W,5 C] buffer (ops.cat_slots) and b, c, d read `a`
+    back out of it; b, c, d are three problems of one launch."""
+
+    RATES = ((1, 6), (18, 15), (6, 21), (1, 1), (6, 3))
+
+    def __init__(self, in_dim, reduction_dim=256, output_stride=16, rates=RATES, dropout=False, separable=False):
+        super().__init__()
+        if dropout:
+            raise NotImplementedError("DPC(dropout=True): get_aspp never sets it")
+        if output_stride == 8:
+            rates = [(2 * r[0], 2 * r[1]) for r in rates]
+        elif output_stride != 16:
+            raise ValueError("output stride of {} not supported".format(output_stride))
+        self.dropout = dropout
+        self.a = dpc_conv(in_dim, reduction_dim, tuple(rates[0]), separable)
+        self.b = dpc_conv(reduction_dim, reduction_dim, tuple(rates[1]), separable)
+        self.c = dpc_conv(reduction_dim, reduction_dim, tuple(rates[2]), separable)
+        self.d = dpc_conv(reduction_dim, reduction_dim, tuple(rates[3]), separable)
+        self.e = dpc_conv(reduction_dim, reduction_dim, tuple(rates[4]), separable)
+        self.drop = nn.Dropout(p=0.1)
+
+    def forward(self, x):
+        B = ops.backend()
+        width = self.a[0].out_channels
+        slots = B.cat_slots(x, [width] * 5)
+        sa, sb, sc, sd, se = slots if slots is not None else [None] * 5      # (None: the result is a new tensor)
+        a = B.dil_conv_bn_act(self.a[0], self.a[1], x, True, out=sa)
+        bcd = [self.b, self.c, self.d]
+        b, c, d = B.dil_conv_bn_act([m[0] for m in bcd], [m[1] for m in bcd], [a, a, a], True,
+                                    out=None if slots is None else [sb, sc, sd])
+        e = B.dil_conv_bn_act(self.e[0], self.e[1], b, True, out=se)
+        return B.cat([a, b, c, d, e])
+
+
 def get_aspp(high_level_ch, bottleneck_ch, output_stride, dpc=False):
     """network/utils.py:301-311"""
-    assert not dpc, "DPC is not on the supported path"
+    if dpc:
+        return DPC(high_level_ch, bottleneck_ch, output_stride=output_stride), 5 * bottleneck_ch
     return AtrousSpatialPyramidPoolingModule(high_level_ch, bottleneck_ch, output_stride=output_stride), 5 * bottleneck_ch
 
 

@@ -18,6 +18,21 @@ class Conv2d(nn.Conv2d):
                                     self.dilation[0], out_f32)
 
 
+class DilConv2d(nn.Conv2d):
+    """nn.Conv2d(Cin, Cout, 3, stride 1, padding = dilation = (dil_h, dil_w), bias = False) on NHWC input: the conv of
+    the Dense Prediction Cell (dpc_conv, network/utils.py:249-260), whose dilation differs per axis.  `Conv2d` above reads
+    `dilation[0]` only, so this layer has a route of its own: ops.dil_conv_bn_act, which takes the BatchNorm behind the
+    conv with it (there is no rectangular conv without one in the reference).  The parameter container is nn.Conv2d's:
+    keys and shapes are torch's."""
+
+    def forward(self, x, bn, relu=True, out=None):
+        """conv -> bn (-> ReLU) of one problem; several layers at once (b, c, d of the cell) go to
+        ops.backend().dil_conv_bn_act as lists."""
+        if out is None:
+            return ops.backend().dil_conv_bn_act(self, bn, x, relu)
+        return ops.backend().dil_conv_bn_act(self, bn, x, relu, out=out)      # (ops.cat_slots placement)
+
+
 class BatchNorm2d(nn.BatchNorm2d):
     """nn.BatchNorm2d with the following add / ReLU / Dropout2d mask fused into
     the normalisation pass: z = post * relu(bn(x) + residual)."""

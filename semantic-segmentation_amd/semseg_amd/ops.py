@@ -136,6 +136,26 @@ class BackendBase:
         y = self.grouped_conv(x, conv.weight, conv.stride[0], conv.dilation[0], conv.groups, want_stats=bn.training)
         return self.batch_norm_act(y, bn, None, relu, None)
 
+    @staticmethod
+    def _dil_conv_check(conv):
+        assert conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.bias is None and conv.groups == 1 and \
+            tuple(conv.padding) == tuple(conv.dilation) and conv.padding_mode == "zeros", \
+            "dil_conv_bn_act takes nn.Conv2d(Cin, Cout, 3, stride 1, padding = dilation = (dh, dw), bias = False)"
+
+    def dil_conv_bn_act(self, conv, bn, x, relu=True, out=None):
+        """3x3 stride-1 `conv` with a dilation per axis, padding = dilation -> bn (-> ReLU): one conv of the Dense
+        Prediction Cell (dpc_conv, network/utils.py:249-260).  x: one problem, or a LIST of independent problems (b, c, d
+        of the cell) with `conv` / `bn` (/ `out`) lists of the same length.  Here the backend's own dense conv primitive
+        with the TUPLE padding / dilation (it ends in F.conv2d, which takes them per axis), so that every backend applies
+        its own rounding model -- the discipline of grouped_conv_bn_act -- then its own BatchNorm.  The HIP backend, whose
+        conv route reads one dilation, overrides this with the kernels of csrc/conv_dil.hip."""
+        assert out is None, "output placement is the HIP backend's (cat_slots returns None here)"
+        if _is_list(x):
+            return [self.dil_conv_bn_act(c, b, xi, relu) for c, b, xi in zip(conv, bn, x)]
+        self._dil_conv_check(conv)
+        y = self._conv2d(x, conv.weight, None, 1, tuple(conv.padding), tuple(conv.dilation))
+        return self.batch_norm_act(y, bn, None, relu, None)
+
     def max_pool3x3s2_ceil(self, x):
         """nn.MaxPool2d(3, stride=2, ceil_mode=True), no padding (network/SEresnext.py:271-272): [B,H,W,C] ->
         [B,H//2,W//2,C] for H, W >= 2; a window that overhangs the edge takes the taps it has."""
@@ -442,6 +462,26 @@ class HipBackend(BackendBase):
                                     want_stats=bn.training)
         return HipBackend.batch_norm_act(self, y, bn, None, relu)
 
+    def dil_conv_bn_act(self, conv, bn, x, relu=True, out=None):
+        """The kernels of csrc/conv_dil.hip; a list of problems shares one group bracket (one launch forward, one for the
+        data gradients).  Training: bn's statistics ride on the conv epilogue.  out: the `cat_slots` channel slice (one
+        per problem) the BatchNorm writes; x may itself be such a slice -- b, c, d read `a` out of the cell's output."""
+        multi = _is_list(x)
+        xs = list(x) if multi else [x]
+        n = len(xs)
+        convs, bns = _lst(conv, n), _lst(bn, n)
+        outs = None if out is None else (list(out) if multi else [out])
+        flat = []
+        for c, xi in zip(convs, xs):
+            self._dil_conv_check(c)
+            if xi.dtype != self.act_dtype:
+                raise NotImplementedError("the rectangular-dilation conv kernels take NHWC %s" % self.act_dtype)
+            flat += [xi, c.weight]
+        spec = tuple((tuple(c.dilation), bool(b.training)) for c, b in zip(convs, bns))
+        ys = self.hb.DilConvGroupFn.apply(spec, *flat)
+        zs = self._bn_group(list(ys), bns, [None] * n, [relu] * n, [None] * n, outs)
+        return zs if multi else zs[0]
+
     def se_gate_add_act(self, se, y, residual=None, relu=True):
         assert not _is_list(y), "se_gate_add_act takes one problem"
         if y.dtype != self.act_dtype or y.shape[3] % 8:
@@ -451,6 +491,8 @@ class HipBackend(BackendBase):
     def cat(self, tensors):
         if len(tensors) == 2 and self.hb.adjacent_slices(tensors[0], tensors[1]):
             return self.hb.CatViewFn.apply(tensors[0], tensors[1])      # both already lie in one buffer (cat_slots)
+        if len(tensors) > 2 and self.hb.slices_of_one_buffer(tensors):
+            return self.hb.CatSlotsFn.apply(*tensors)                   # the same for the Dense Prediction Cell's five
         return torch.cat(tensors, dim=3)      # pure data movement
 
     def to_act(self, x):
